@@ -9,7 +9,13 @@ by the HIP generator before the timed region, so `value` is whole-job
 frames/s with inputs resident in HBM.  One process per GPU; streams are
 independent (no data-path collective); N>1 is weak scaling.
 
-  python bench.py --gpus 1 --steps 200 --warmup 10
+A plain run sets up, pre-rolls every stream to the steady state, warms up, times
+exactly --steps steps once and prints the headline line (`value`, `ms_per_step`).
+--full adds the per-kernel HIP events and roofline objects, the checks, further
+timed windows and legs, the CPU baseline and the pre-decimated run.
+
+  python bench.py --gpus 1 --steps 200 --warmup 10 [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps 200 --warmup 10 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -251,12 +257,24 @@ def main():
                     help="no GPU work: the launch contract only — rank discovery, stream partition, barriers, max-over-ranks timing, "
                          "the JSON line (dry_run: true) — with a rank-dependent sleep as the step; what tests/test_abi_and_host.py "
                          "runs at world 8 over gloo on a CPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline figure: per-family HIP events and the roofline "
+                         "objects, the duplicate-stream and ATE checks, host accounting, the value_spread, value_super_window, "
+                         "value_host_input and roofline_solo legs, the CPU baseline and the value_predecimated run.  The options of "
+                         "those legs take effect only with --full.  Without it the run sets up, pre-rolls, warms up, times exactly "
+                         "--steps steps once and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the per-stream results the last timed step returned (rank 0's streams) "
+                         "as DIR/<field>.npy, float64, one row per stream")
     args = ap.parse_args()
     if args.dry_run:
         return dry_run(args)
     full_res = not args.pre_decimated
     if args.secondary_streams < 0:        # (a small --streams run of a test or a latency script must not spawn a 12288-stream child)
         args.secondary_streams = 12288 if (args.streams <= 0 and full_res) else 0
+    if not args.full:                     # a plain run does only what the headline figure needs
+        args.no_cpu_baseline = True
+        args.spread_windows = args.super_windows = args.host_input_steps = args.solo_steps = args.secondary_streams = 0
 
     import torch
     svs = importlib.import_module("stereovision-slam_amd")
@@ -354,8 +372,9 @@ def main():
         seeds[twin_of_0] = seeds[0]     # one deliberate duplicate: must come out bit-identical (checked below)
 
     def render_block(frame0):
-        """frames [frame0, frame0 + FB) of every stream -> HBM, layout [stream][FB][img]"""
-        svs.synth_render_streams_device(seeds, frame0, FB, SW, SH, d_left, d_right, device=local_rank, cam=cam_r)
+        """frames [frame0, frame0 + FB) of every stream -> HBM, layout [stream][FB][img]; full-size frames are rendered at the
+        pixels the fused 1/2 decimation samples only (the same results as a full render, a quarter of the rendering time)"""
+        svs.synth_render_streams_device(seeds, frame0, FB, SW, SH, d_left, d_right, device=local_rank, cam=cam_r, sampled=full_res)
 
     def barrier():
         rk.barrier()
@@ -416,7 +435,7 @@ def main():
     # shader clock under load: one wave on a HIP stream of its own spins through (most of) a window and reports the engine
     # clock it saw (clock64 against the constant 100 MHz counter) — what a window's kernels ran at
     probe = None
-    if torch.cuda.is_available() and os.environ.get("SVS_BENCH_CLOCK_PROBE", "1") == "1":
+    if args.full and torch.cuda.is_available() and os.environ.get("SVS_BENCH_CLOCK_PROBE", "1") == "1":
         try:
             probe = svs.Context(W, H, max_slots=1, max_jobs=1, max_pts=64, max_corners=16, max_kf=0, max_lm=0, max_obs=0, device=local_rank)
         except Exception:   # noqa: BLE001
@@ -505,8 +524,9 @@ def main():
         run_all(0, 1, False)
         ring["next"] += 1
     c0 = counters_sum()
-    for c in ctxs:
-        c.timing(True)
+    if args.full:
+        for c in ctxs:
+            c.timing(True)
     # the per-frame results of the timed region (88 B per frame: the bench's own log) are allocated and touched here, so
     # that rss_growth_bytes_per_frame below is the growth of the pipeline / library, not of this script's arrays
     res_bufs = [np.zeros((K, Sg), pl.RESULT_DTYPE) for _ in range(G)]
@@ -516,7 +536,9 @@ def main():
     first_timed_frame = ring["next"]
     acct = {"cpu": 0.0, "minflt": 0, "threads": {}}
     # ---- the K timed steps (the window the per-family HIP events, the result log and the checks belong to)
-    t_timed, nblocks = timed(K, True, res_bufs, acct)
+    t_timed, nblocks = timed(K, True, res_bufs, acct if args.full else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, np.concatenate([b_[-1] for b_ in res_bufs]))
     clocks = []
     blocks_hint = [0] * nblocks      # (the clock probe runs beside single-block windows only: a block boundary renders frames)
     cpu_timed, minflt_timed, tc_acc = acct["cpu"], acct["minflt"], acct["threads"]
@@ -528,11 +550,12 @@ def main():
     c1 = counters_sum()
     cnt = {k: c1[k] - c0[k] for k in c1}
     fam_t = {}
-    for f in list(svs.FAMILIES) + list(svs.KERNEL_FAMILIES):
-        parts = [c.timing_get(f) for c in ctxs]
-        fam_t[f] = (sum(p[0] for p in parts), sum(p[1] for p in parts), sum(p[2] for p in parts))
-    for c in ctxs:
-        c.timing(False)
+    if args.full:
+        for f in list(svs.FAMILIES) + list(svs.KERNEL_FAMILIES):
+            parts = [c.timing_get(f) for c in ctxs]
+            fam_t[f] = (sum(p[0] for p in parts), sum(p[1] for p in parts), sum(p[2] for p in parts))
+        for c in ctxs:
+            c.timing(False)
 
     # ---- value_spread: further windows of K steps, same process, same operating point (the 0.6-s
     #      window of the driver's 20 steps scatters by +-10 % from run to run; here is the scatter inside one run).
@@ -620,53 +643,20 @@ def main():
                         "to back on one HIP stream, so every launch has the whole chip (no co-resident kernels of other "
                         "groups); same accounting as roofline_by_family" % (Sg, Ks))
     res = np.concatenate(res_g, axis=1)
-    import ctypes as _C
-    hostns = np.zeros(8)
-    for c in ctxs:
-        o = (_C.c_longlong * 8)()
-        c.L.svslam_debug_host_ns(c.h, o)
-        hostns += np.array(list(o), float)
-
     ok_frames = int((res["status"] != 3).sum())      # not LOST
-    # full-size checks that need no oracle: (1) the duplicated stream, processed by another group /
-    # context / batch position, reproduces stream 0 bit for bit; (2) trajectory error against the
-    # renderer's ground truth on a sample of streams (timed region only, aligned at its first frame)
-    replica_ok = bool(twin_of_0 == 0 or (np.array_equal(res["pose"][:, 0], res["pose"][:, twin_of_0]) and
-                                         np.array_equal(res["n_inliers"][:, 0], res["n_inliers"][:, twin_of_0])))
-    ate = []
-    for s_ in range(0, S, max(1, S // 16))[:16]:
-        gt = np.array([svs.synth_gt(seeds[s_], first_timed_frame + f) for f in range(K)])
-        ate.append(pl.ate_rmse(res["pose"][:, s_], gt))
     rank_rows = rank_table(rk, sdist, local_rank, pinned, seeds)
     total_frames = S * K * world
     value_first = total_frames / elapsed
     # `value` is the MEDIAN window: every window is exactly K steps between barrier + synchronize on both
     # sides, max over ranks; the first one carries the per-family HIP events and the result log, the others do not.  With an
     # even count the lower of the two middle windows is taken, so that ms_per_step belongs to a window that was really timed.
+    # A plain run (no --full) times the first window alone.
     windows = sorted([value_first] + list(spread))
     value = windows[(len(windows) - 1) // 2]
     elapsed_value = total_frames / value
     ranks_seen = int(round(rk.sum_over_ranks(1.0)))      # an all-reduce of ones over the job's communicator (1 without a process group)
 
     if rank == 0:
-        # The dominant KERNEL: the interval with the largest summed HIP-event time among those that enclose one kernel (ba_solve =
-        # k_local_ba_t alone; pyramid, lk, pose_only, triangulate are one kernel each; gftt is two short ones and counted as one).
-        # "local_ba" (gather + build + solver + scatter) is a family of four kernels: priced in roofline_by_family, not here.
-        single = [f for f in fam_t if f != "local_ba"]
-        dom = max(single, key=lambda f: fam_t[f][0])
-        ms, launches, _ = fam_t[dom]
-        abytes = algorithmic_bytes(dom, cnt, launches)
-        avg_s = (ms / 1e3) / max(launches, 1)
-        achieved = (abytes / max(launches, 1)) / max(avg_s, 1e-12) / 1e9
-        dom_traffic_fam = dom if measured_traffic(dom, cnt, launches) is not None else ("local_ba" if dom == "ba_solve" else dom)
-        by_fam = {}
-        for f, (fms, fl, _) in fam_t.items():
-            fb = algorithmic_bytes(f, cnt, fl)
-            if fl and fms > 0:
-                by_fam[f] = {"achieved": round(fb / (fms / 1e3) / 1e9, 2), "frac": round(fb / (fms / 1e3) / 1e9 / HBM_PEAK_GBS, 6),
-                             "avg_launch_us": round(1e3 * fms / fl, 2), "launches": fl, "kernels": svs.FAMILY_KERNELS.get(f),
-                             "algorithmic_bytes_per_launch": round(fb / fl, 1)}
-        all_bytes = sum(algorithmic_bytes(f, cnt, fam_t[f][1]) for f in svs.FAMILIES)
         build_info = svs.load().svslam_build_info().decode()
         ctx_xtol = ctx.pose_only_xtol_effective()
         out = {
@@ -679,11 +669,6 @@ def main():
             "ranks": rank_rows,
             "steps": K, "warmup": Wm,
             "ms_per_step": round(1e3 * elapsed_value / K, 4), "higher_is_better": True, "scaling": "weak",
-            "value_windows": {"n": len(windows), "median": round(value, 2), "min": round(windows[0], 2), "max": round(windows[-1], 2),
-                              "first": round(value_first, 2), "first_ms_per_step": round(1e3 * elapsed / K, 4),
-                              "how": "value = median of the first timed window (the one the per-family HIP events, the roofline "
-                                     "objects and the checks belong to) and the value_spread windows; each window is exactly "
-                                     "--steps steps between barrier + synchronize, max over ranks"},
             "vs_baseline": None, "dtype": "u8/i32 fixed-point (pyramid, LK), f32 (GFTT), f64 (LM, BA)",
             "data": "synthetic",
             "config": {"workload": "configs[1..3] on synthetic input: full Frontend::AddFrame hot path on HIP "
@@ -708,67 +693,108 @@ def main():
                                            "lm_iterations": round(cnt["ba_iters"] / max(cnt["ba_calls"], 1), 2)},
                        "per_frame_mean": {"tracked_points": round(cnt["track_pts"] / max(cnt["frames"], 1), 1),
                                           "pose_edges": round(cnt["pose_edges"] / max(cnt["frames"], 1), 1)}, "tracked_ok_fraction": ok_frames / (S * K),
-                       "checks": {"duplicate_stream_bit_identical": replica_ok,
-                                  "ate_rmse_m_mean_of_%d_streams" % len(ate): round(float(np.mean(ate)), 4),
-                                  "ate_rmse_m_max": round(float(np.max(ate)), 4)},
                        "parallelism": "%d independent streams/GPU x %d GPU(s), no collective" % (S, world)},
-            "roofline": {"bound": "hbm", "kernel": "+".join(svs.FAMILY_KERNELS.get(dom, [dom])), "interval": dom,
-                         "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
-                         "peak_measured": HBM_PEAK_MEASURED_GBS, "frac_of_peak_measured": round(achieved / HBM_PEAK_MEASURED_GBS, 6),
-                         "traffic": measured_traffic(dom_traffic_fam, cnt, launches),
-                         "traffic_source": "committed PMC passes (profiles/pmc_traffic.json, tools/pmc_traffic.sh: FETCH_SIZE and WRITE_SIZE in "
-                                           "separate runs over the launches of a timed window, FETCH_SIZE x 2 on gfx950), not measured by this run"
-                                           + ("; the figure is the whole local_ba family's (gather + build + solver + scatter)" if dom_traffic_fam != dom else ""),
-                         "traffic_stamp": pmc_stamp("pmc_traffic.json", build_info),
-                         "avg_launch_us": round(avg_s * 1e6, 2), "launches": launches,
-                         "algorithmic_bytes_per_launch": round(abytes / max(launches, 1), 1),
-                         "how": "HIP events on the launching stream around this kernel only, summed over the first timed window's launches "
-                                "(kernels of the other host threads' streams run beside it); the rocprofv3 --kernel-trace --stats row of the "
-                                "same command is profiles/r6_bench_default_kernel_stats.csv"},
-            # every kernel family priced the same way (launches of different groups overlap, so each
-            # family's duration is its own HIP-event time, not a share of the wall clock), and the
-            # whole step: all algorithmic bytes of the timed region over its wall time
-            "roofline_by_family": by_fam,
-            "roofline_compute": {f: compute_side(f, cnt, fam_t[f][0]) for f in ("local_ba", "lk") if fam_t[f][1]},
-            "roofline_valu_step": valu_step(cnt, t_timed),
-            "roofline_solo": solo,
-            "pmc_stamps": {f: pmc_stamp(f, build_info) for f in ("pmc_traffic.json", "pmc_valu.json", "pmc_valu_step.json")},
-            "value_super_window": super_window,
-            "value_spread": {"windows": [round(v, 1) for v in spread], "keyframes": spread_kf, "keyframes_first_window": cnt["keyframes"], "steps_each": K,
-                             "shader_clock_mhz": clocks,
-                             "hip_events": "only the first window records the per-family HIP events (pyramid, lk, gftt, triangulate, pose_only, local_ba, "
-                                           "ba_solve) and writes the per-frame result log; the spread windows and the super-window record none",
-                             "min": round(min(spread), 1) if spread else None, "max": round(max(spread), 1) if spread else None,
-                             "mean": round(float(np.mean(spread)), 1) if spread else None,
-                             "rel_std": round(float(np.std(spread) / np.mean(spread)), 4) if spread else None,
-                             "how": "further windows of the same length timed in the same process after the reported one"},
-            "value_host_input": host_input,
-            "roofline_whole_step": {"achieved": round(all_bytes * world / elapsed / 1e9, 2), "unit": "GB/s (all ranks)",
-                                    "frac_of_peak_per_gpu": round(all_bytes / elapsed / 1e9 / HBM_PEAK_GBS, 6),
-                                    "algorithmic_bytes_per_frame": round(all_bytes / max(cnt["frames"], 1), 1)},
-            "kernel_ms": {f: round(fam_t[f][0], 3) for f in fam_t},
-            # unit counts since process start (pre-roll and warm-up included): what a PMC pass over the whole
-            # process divides its per-kernel totals by (tools/pmc_traffic.sh)
-            "units_whole_process": {k: c1[k] for k in ("frames", "keyframes", "ba_calls", "gftt_calls", "pyr_left", "pyr_right",
-                                                       "track_pts", "right_pts", "tri_pts", "pose_edges") if k in c1},
-            # the same counts for the first timed window alone, with the launches of every family in it: a PMC pass over a run whose
-            # LAST launches are this window (no further legs) prices the steady state, not the pre-roll's growing windows (tools/pmc_reduce.py)
-            "units_timed_window": {**{k: cnt[k] for k in ("frames", "keyframes", "ba_calls", "gftt_calls", "pyr_left", "pyr_right",
-                                                          "track_pts", "right_pts", "tri_pts", "pose_edges") if k in cnt},
-                                   "launches": {f: fam_t[f][1] for f in fam_t}},
-            "host_ms_per_step": {"in_step": round(cnt["ns_step"] / 1e6 / K / G, 3),
-                                 "in_abi_calls": round(cnt["ns_kernel_calls"] / 1e6 / K / G, 3),
-                                 "h2d_enqueue": round(hostns[0] / 1e6 / K / G, 3), "d2h_enqueue": round(hostns[1] / 1e6 / K / G, 3),
-                                 "stream_wait": round(hostns[2] / 1e6 / K / G, 3), "event_collect": round(hostns[5] / 1e6 / K / G, 3), "ba_host_prep": round(hostns[4] / 1e6 / K / G, 3),
-                                 "cpus_busy": round(cpu_busy, 2), "cpus_allowed": effective_cpus(),
-                                 "pinned_to_gpu_numa_cpus": len(pinned),
-                                 "minor_page_faults_per_step": round(minflt_timed / K, 1),
-                                 "rss_growth_bytes_per_frame": round((rss1 - rss0) / max(S * K, 1), 1),
-                                 "rss_gb": round(rss1 / 1e9, 2),
-                                 "cpus_busy_by_thread_name": cpu_by_thread,
-                             "capacity_events": {"corners_dropped": cnt.get("corners_dropped", 0), "ba_skipped": cnt.get("ba_skipped", 0)}},
         }
+        if args.full:
+            # full-size checks that need no oracle: (1) the duplicated stream, processed by another group /
+            # context / batch position, reproduces stream 0 bit for bit; (2) trajectory error against the
+            # renderer's ground truth on a sample of streams (timed region only, aligned at its first frame)
+            replica_ok = bool(twin_of_0 == 0 or (np.array_equal(res["pose"][:, 0], res["pose"][:, twin_of_0]) and
+                                                 np.array_equal(res["n_inliers"][:, 0], res["n_inliers"][:, twin_of_0])))
+            ate = []
+            for s_ in range(0, S, max(1, S // 16))[:16]:
+                gt = np.array([svs.synth_gt(seeds[s_], first_timed_frame + f) for f in range(K)])
+                ate.append(pl.ate_rmse(res["pose"][:, s_], gt))
+            import ctypes as _C
+            hostns = np.zeros(8)
+            for c in ctxs:
+                o = (_C.c_longlong * 8)()
+                c.L.svslam_debug_host_ns(c.h, o)
+                hostns += np.array(list(o), float)
+            out["value_windows"] = {"n": len(windows), "median": round(value, 2), "min": round(windows[0], 2), "max": round(windows[-1], 2),
+                                    "first": round(value_first, 2), "first_ms_per_step": round(1e3 * elapsed / K, 4),
+                                    "how": "value = median of the first timed window (the one the per-family HIP events, the roofline "
+                                           "objects and the checks belong to) and the value_spread windows; each window is exactly "
+                                           "--steps steps between barrier + synchronize, max over ranks"}
+            out["config"]["checks"] = {"duplicate_stream_bit_identical": replica_ok,
+                                       "ate_rmse_m_mean_of_%d_streams" % len(ate): round(float(np.mean(ate)), 4),
+                                       "ate_rmse_m_max": round(float(np.max(ate)), 4)}
+            # The dominant KERNEL: the interval with the largest summed HIP-event time among those that enclose one kernel (ba_solve =
+            # k_local_ba_t alone; pyramid, lk, pose_only, triangulate are one kernel each; gftt is two short ones and counted as one).
+            # "local_ba" (gather + build + solver + scatter) is a family of four kernels: priced in roofline_by_family, not here.
+            single = [f for f in fam_t if f != "local_ba"]
+            dom = max(single, key=lambda f: fam_t[f][0])
+            ms, launches, _ = fam_t[dom]
+            abytes = algorithmic_bytes(dom, cnt, launches)
+            avg_s = (ms / 1e3) / max(launches, 1)
+            achieved = (abytes / max(launches, 1)) / max(avg_s, 1e-12) / 1e9
+            dom_traffic_fam = dom if measured_traffic(dom, cnt, launches) is not None else ("local_ba" if dom == "ba_solve" else dom)
+            by_fam = {}
+            for f, (fms, fl, _) in fam_t.items():
+                fb = algorithmic_bytes(f, cnt, fl)
+                if fl and fms > 0:
+                    by_fam[f] = {"achieved": round(fb / (fms / 1e3) / 1e9, 2), "frac": round(fb / (fms / 1e3) / 1e9 / HBM_PEAK_GBS, 6),
+                                 "avg_launch_us": round(1e3 * fms / fl, 2), "launches": fl, "kernels": svs.FAMILY_KERNELS.get(f),
+                                 "algorithmic_bytes_per_launch": round(fb / fl, 1)}
+            all_bytes = sum(algorithmic_bytes(f, cnt, fam_t[f][1]) for f in svs.FAMILIES)
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": "+".join(svs.FAMILY_KERNELS.get(dom, [dom])), "interval": dom,
+                             "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
+                             "peak_measured": HBM_PEAK_MEASURED_GBS, "frac_of_peak_measured": round(achieved / HBM_PEAK_MEASURED_GBS, 6),
+                             "traffic": measured_traffic(dom_traffic_fam, cnt, launches),
+                             "traffic_source": "committed PMC passes (profiles/pmc_traffic.json, tools/pmc_traffic.sh: FETCH_SIZE and WRITE_SIZE in "
+                                               "separate runs over the launches of a timed window, FETCH_SIZE x 2 on gfx950), not measured by this run"
+                                               + ("; the figure is the whole local_ba family's (gather + build + solver + scatter)" if dom_traffic_fam != dom else ""),
+                             "traffic_stamp": pmc_stamp("pmc_traffic.json", build_info),
+                             "avg_launch_us": round(avg_s * 1e6, 2), "launches": launches,
+                             "algorithmic_bytes_per_launch": round(abytes / max(launches, 1), 1),
+                             "how": "HIP events on the launching stream around this kernel only, summed over the first timed window's launches "
+                                    "(kernels of the other host threads' streams run beside it); the rocprofv3 --kernel-trace --stats row of the "
+                                    "same command is profiles/r6_bench_default_kernel_stats.csv"},
+                # every kernel family priced the same way (launches of different groups overlap, so each
+                # family's duration is its own HIP-event time, not a share of the wall clock), and the
+                # whole step: all algorithmic bytes of the timed region over its wall time
+                "roofline_by_family": by_fam,
+                "roofline_compute": {f: compute_side(f, cnt, fam_t[f][0]) for f in ("local_ba", "lk") if fam_t[f][1]},
+                "roofline_valu_step": valu_step(cnt, t_timed),
+                "roofline_solo": solo,
+                "pmc_stamps": {f: pmc_stamp(f, build_info) for f in ("pmc_traffic.json", "pmc_valu.json", "pmc_valu_step.json")},
+                "value_super_window": super_window,
+                "value_spread": {"windows": [round(v, 1) for v in spread], "keyframes": spread_kf, "keyframes_first_window": cnt["keyframes"], "steps_each": K,
+                                 "shader_clock_mhz": clocks,
+                                 "hip_events": "only the first window records the per-family HIP events (pyramid, lk, gftt, triangulate, pose_only, local_ba, "
+                                               "ba_solve) and writes the per-frame result log; the spread windows and the super-window record none",
+                                 "min": round(min(spread), 1) if spread else None, "max": round(max(spread), 1) if spread else None,
+                                 "mean": round(float(np.mean(spread)), 1) if spread else None,
+                                 "rel_std": round(float(np.std(spread) / np.mean(spread)), 4) if spread else None,
+                                 "how": "further windows of the same length timed in the same process after the reported one"},
+                "value_host_input": host_input,
+                "roofline_whole_step": {"achieved": round(all_bytes * world / elapsed / 1e9, 2), "unit": "GB/s (all ranks)",
+                                        "frac_of_peak_per_gpu": round(all_bytes / elapsed / 1e9 / HBM_PEAK_GBS, 6),
+                                        "algorithmic_bytes_per_frame": round(all_bytes / max(cnt["frames"], 1), 1)},
+                "kernel_ms": {f: round(fam_t[f][0], 3) for f in fam_t},
+                # unit counts since process start (pre-roll and warm-up included): what a PMC pass over the whole
+                # process divides its per-kernel totals by (tools/pmc_traffic.sh)
+                "units_whole_process": {k: c1[k] for k in ("frames", "keyframes", "ba_calls", "gftt_calls", "pyr_left", "pyr_right",
+                                                           "track_pts", "right_pts", "tri_pts", "pose_edges") if k in c1},
+                # the same counts for the first timed window alone, with the launches of every family in it: a PMC pass over a run whose
+                # LAST launches are this window (no further legs) prices the steady state, not the pre-roll's growing windows (tools/pmc_reduce.py)
+                "units_timed_window": {**{k: cnt[k] for k in ("frames", "keyframes", "ba_calls", "gftt_calls", "pyr_left", "pyr_right",
+                                                              "track_pts", "right_pts", "tri_pts", "pose_edges") if k in cnt},
+                                       "launches": {f: fam_t[f][1] for f in fam_t}},
+                "host_ms_per_step": {"in_step": round(cnt["ns_step"] / 1e6 / K / G, 3),
+                                     "in_abi_calls": round(cnt["ns_kernel_calls"] / 1e6 / K / G, 3),
+                                     "h2d_enqueue": round(hostns[0] / 1e6 / K / G, 3), "d2h_enqueue": round(hostns[1] / 1e6 / K / G, 3),
+                                     "stream_wait": round(hostns[2] / 1e6 / K / G, 3), "event_collect": round(hostns[5] / 1e6 / K / G, 3), "ba_host_prep": round(hostns[4] / 1e6 / K / G, 3),
+                                     "cpus_busy": round(cpu_busy, 2), "cpus_allowed": effective_cpus(),
+                                     "pinned_to_gpu_numa_cpus": len(pinned),
+                                     "minor_page_faults_per_step": round(minflt_timed / K, 1),
+                                     "rss_growth_bytes_per_frame": round((rss1 - rss0) / max(S * K, 1), 1),
+                                     "rss_gb": round(rss1 / 1e9, 2),
+                                     "cpus_busy_by_thread_name": cpu_by_thread,
+                                 "capacity_events": {"corners_dropped": cnt.get("corners_dropped", 0), "ba_skipped": cnt.get("ba_skipped", 0)}},
+            })
         if world == 1 and not args.no_cpu_baseline:
             base = cpu_baseline(svs, pl, ctx, cfg, seeds, max(pre, 0), args.cpu_frames, local_rank, cam_r, (SW, SH),
                                 effective_cpus())
@@ -787,7 +813,7 @@ def main():
         #      BASELINE.json's metric names and the pre-decimated run is this named secondary (more streams fit: 12288).
         if run_secondary:
             import subprocess
-            cmd = [sys.executable, os.path.abspath(__file__), "--pre-decimated", "--streams", str(args.secondary_streams), "--steps", str(K),
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--pre-decimated", "--streams", str(args.secondary_streams), "--steps", str(K),
                    "--warmup", str(Wm), "--no-cpu-baseline", "--spread-windows", "2", "--super-windows", "0", "--host-input-steps", "0", "--solo-steps", "0",
                    "--predecimated-streams", "0"]
             # the child is a single process of its own: it must not join the parent's rendezvous
@@ -811,6 +837,14 @@ def main():
                 out["value_predecimated"] = {"error": repr(e)[:300]}
         print(json.dumps(out), flush=True)
     rk.close()
+
+
+def dump_outputs(d, last):
+    """--dump-outputs: the FrameResult record of every stream after the last timed step (what svs_pipe_run_device hands its
+    caller), one float64 array per field (pose [S, 7], status [S], ...); every integer field is exact in float64"""
+    os.makedirs(d, exist_ok=True)
+    for name in last.dtype.names:
+        np.save(os.path.join(d, name + ".npy"), last[name].astype(np.float64))
 
 
 def _vp(v):

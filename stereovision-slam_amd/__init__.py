@@ -593,10 +593,13 @@ def synth_views(seed, frame, cam=KITTI00_HALF_CAM, baseline=KITTI00_BASELINE):
 
 
 def synth_render_streams_device(seeds, frame0, nframes, w, h, d_left, d_right, device=0, cam=KITTI00_HALF_CAM,
-                                baseline=KITTI00_BASELINE, block=4096):
+                                baseline=KITTI00_BASELINE, block=4096, sampled=False):
     """render frames [frame0, frame0 + nframes) of every stream in `seeds` into the device buffers
-    d_left / d_right, laid out [stream][nframes][h*w]; a few launches per `block` images."""
+    d_left / d_right, laid out [stream][nframes][h*w]; a few launches per `block` images.  sampled: only the pixels
+    (2x, 2y), each replicated into its 2x2 block — for full-size frames that the pipeline decimates by 1/2 (src_width /
+    src_height), whose results are then bit-identical to those of a full render, at a quarter of the rendering work."""
     n = len(seeds)
+    render = load().svslam_synth_render_batch_sampled if sampled else load().svslam_synth_render_batch
     per = max(1, block // max(nframes, 1))            # streams per launch
     camv = (C.c_double * 4)(*cam)
     img = w * h
@@ -606,7 +609,7 @@ def synth_render_streams_device(seeds, frame0, nframes, w, h, d_left, d_right, d
         vl = (SynthView * (m * nframes))(); vr = (SynthView * (m * nframes))()
         synth_lib().svs_synth_make_views_batch(m, sd, frame0, nframes, camv, C.c_double(baseline), vl, vr)
         for arr, base in ((vl, d_left), (vr, d_right)):
-            rc = load().svslam_synth_render_batch(device, m * nframes, arr, w, h, C.c_void_p(base + s0 * nframes * img))
+            rc = render(device, m * nframes, arr, w, h, C.c_void_p(base + s0 * nframes * img))
             if rc != 0:
                 raise RuntimeError("svslam_synth_render_batch failed (%d)" % rc)
 

@@ -213,13 +213,13 @@ def test_pipeline_low_latency_shape_matches_cpu_twin(svs):
 
 
 def test_bench_contract_small_run():
-    """bench.py prints exactly one JSON line with the driver's keys plus roofline and cpu_baseline."""
+    """bench.py --full prints exactly one JSON line with the driver's keys plus roofline and cpu_baseline."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "3",
-                          "--streams", "16", "--groups", "2", "--host-threads", "1", "--cpu-frames", "40"],
+                          "--streams", "16", "--groups", "2", "--host-threads", "1", "--cpu-frames", "40", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -252,6 +252,65 @@ def test_bench_contract_small_run():
     assert d["value_super_window"]["steps"] == 36 and d["value_super_window"]["value"] > 0
     a = d["cpu_baseline_all_cores"]
     assert a["kind"] == "port" and a["cores"] >= 1 and a["value"] >= 0.8 * c["value"]
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """bench.py without --full: one JSON line with the headline keys and none of the --full legs; the timed window is exactly
+    --steps steps; --dump-outputs writes the per-stream results of the last timed step (float64, stream order), and two runs
+    with the same arguments dump the same arrays."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    S, K, Wm = 16, 5, 2
+    fields = ("pose", "status", "is_keyframe", "n_features", "n_inliers", "frame_id", "keyframe_id")
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(Wm),
+                              "--streams", str(S), "--groups", "2", "--host-threads", "1", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        r = json.loads(lines[0])
+        assert r["steps"] == K and r["warmup"] == Wm and r["unit"] == "frames/s" and r["higher_is_better"] is True
+        assert r["metric"].startswith("stereo frames/sec") and r["dtype"].startswith("u8/i32")
+        assert abs(r["value"] - S * K / (r["ms_per_step"] * K * 1e-3)) <= 1e-3 * r["value"]
+        for k in ("roofline", "kernel_ms", "cpu_baseline", "value_windows", "value_spread", "value_super_window", "host_ms_per_step"):
+            assert k not in r, k
+        assert "checks" not in r["config"] and r["config"]["streams_per_gpu"] == S
+        a = {f: np.load(str(d / (f + ".npy"))) for f in fields}
+        assert sorted(os.listdir(d)) == sorted(f + ".npy" for f in fields)
+        assert all(v.dtype == np.float64 and len(v) == S for v in a.values()) and a["pose"].shape == (S, 7)
+        assert (a["frame_id"] == r["config"]["preroll_steps"] + Wm + K - 1).all()
+        assert np.array_equal(a["pose"][0], a["pose"][S // 2])     # the duplicated stream (first of the second group)
+        dumps.append(a)
+    for f in fields:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
+def test_sampled_render_is_the_full_render_where_the_decimation_samples(svs):
+    """synth_render_streams_device(sampled=True), what bench.py renders its full-size frames with: the pixels (2x, 2y) are those of
+    a full render and each fills its 2x2 block (1241 columns: the last sampled column has no right neighbour)"""
+    SW, SH, F = 1241, 376, 2
+    seeds = [11, 12, 13]
+    cam2 = tuple(2 * v for v in svs.KITTI00_HALF_CAM)
+    ctx = svs.Context(620, 188, max_slots=1, max_jobs=1)
+    bufs = [ctx.dev_alloc(len(seeds) * F * SW * SH) for _ in range(4)]
+    svs.synth_render_streams_device(seeds, 5, F, SW, SH, bufs[0], bufs[1], cam=cam2)
+    svs.synth_render_streams_device(seeds, 5, F, SW, SH, bufs[2], bufs[3], cam=cam2, sampled=True)
+    imgs = []
+    for b in bufs:
+        a = np.zeros((len(seeds) * F, SH, SW), np.uint8)
+        ctx.dev_download(b, a)
+        imgs.append(a)
+        ctx.dev_free(b)
+    ctx.close()
+    for full, smp in ((imgs[0], imgs[2]), (imgs[1], imgs[3])):
+        kept = full[:, ::2, ::2]
+        assert np.array_equal(smp[:, ::2, ::2], kept)
+        assert np.array_equal(smp, np.repeat(np.repeat(kept, 2, 1), 2, 2)[:, :SH, :SW])
 
 
 def test_pipeline_config2_hip_frontend_with_cpu_backend(svs):

@@ -17,7 +17,7 @@ def test_scale_launch_at_the_visible_device_count(svs):
     n = svs.load().svslam_device_count()
     assert n >= 1
     args = ["--steps", "6", "--warmup", "2", "--streams", "768", "--no-cpu-baseline", "--spread-windows", "0",
-            "--host-input-steps", "0", "--solo-steps", "0", "--full-res-streams", "0"]
+            "--host-input-steps", "0", "--solo-steps", "0", "--full-res-streams", "0", "--full"]
     env = dict(os.environ, SCALE_PORT="29547")
     r = subprocess.run(["bash", os.path.join(ROOT, "tools", "scale.sh"), str(n)] + args, capture_output=True, text=True,
                        timeout=900, env=env)

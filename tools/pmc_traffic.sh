@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 mkdir -p gpurun_out
 for ctr in FETCH_SIZE WRITE_SIZE; do
   O=gpurun_out/pmc_$ctr; rm -rf "$O"; mkdir -p "$O"
-  timeout ${PMC_TIMEOUT:-400} rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d "$O" -- python bench.py ${PMC_BENCH_ARGS:---streams 256 --groups 1 --host-threads 4 --steps 30 --warmup 5 --preroll 100} --no-cpu-baseline --spread-windows 0 --super-windows 0 --host-input-steps 0 --solo-steps 0 --predecimated-streams 0 > gpurun_out/pmc_${ctr}_bench.json 2> gpurun_out/pmc_${ctr}.err < /dev/null
+  timeout ${PMC_TIMEOUT:-400} rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d "$O" -- python bench.py --full ${PMC_BENCH_ARGS:---streams 256 --groups 1 --host-threads 4 --steps 30 --warmup 5 --preroll 100} --no-cpu-baseline --spread-windows 0 --super-windows 0 --host-input-steps 0 --solo-steps 0 --predecimated-streams 0 > "$O"_bench.json 2> "$O".err < /dev/null
   python tools/pmc_reduce.py "$O" gpurun_out/pmc_${ctr}_bench.json $ctr > gpurun_out/pmc_${ctr}_reduced.json
 done
 python - <<'PY'

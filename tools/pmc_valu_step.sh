@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/pmc_valu_step; rm -rf $O; mkdir -p $O
-timeout ${PMC_TIMEOUT:-900} rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU --kernel-trace --output-format csv -d "$O" -- python bench.py ${PMC_BENCH_ARGS:---streams 2048 --groups 2 --steps 20 --warmup 5} --no-cpu-baseline --spread-windows 0 --super-windows 0 --host-input-steps 0 --solo-steps 0 --predecimated-streams 0 > gpurun_out/pmc_valu_step_bench.json 2> gpurun_out/pmc_valu_step.err < /dev/null
+timeout ${PMC_TIMEOUT:-900} rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU --kernel-trace --output-format csv -d "$O" -- python bench.py --full ${PMC_BENCH_ARGS:---streams 2048 --groups 2 --steps 20 --warmup 5} --no-cpu-baseline --spread-windows 0 --super-windows 0 --host-input-steps 0 --solo-steps 0 --predecimated-streams 0 > "$O"_bench.json 2> "$O".err < /dev/null
 python tools/pmc_reduce.py $O gpurun_out/pmc_valu_step_bench.json SQ_INSTS_VALU SQ_INSTS_SALU > gpurun_out/pmc_valu_step_raw.json
 python - <<'PY'
 import json

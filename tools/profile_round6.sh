@@ -17,18 +17,18 @@ parts="${*:-bench rocprof kbench latency pmc_valu pmc_step pmc_traffic}"
 has() { case " $parts " in *" $1 "*) return 0;; esac; return 1; }
 QUIET="--no-cpu-baseline --host-input-steps 0 --solo-steps 0 --predecimated-streams 0"
 if has bench; then
-( time timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err < /dev/null ) 2> $O/bench_default.time
-timeout 900 bash tools/scale.sh 1 --steps 20 --warmup 5 > $O/scale_n1.json 2> $O/scale_n1.err < /dev/null
+( time timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err < /dev/null ) 2> $O/bench_default.time
+timeout 900 bash tools/scale.sh 1 --full --steps 20 --warmup 5 > $O/scale_n1.json 2> $O/scale_n1.err < /dev/null
 fi
 if has rocprof; then
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp -o rp -- python bench.py --no-cpu-baseline --spread-windows 0 --super-windows 0 --host-input-steps 0 --predecimated-streams 0 > $O/bench_under_rocprof.json 2> $O/rocprof.err < /dev/null
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp -o rp -- python bench.py --full --no-cpu-baseline --spread-windows 0 --super-windows 0 --host-input-steps 0 --predecimated-streams 0 > $O/bench_under_rocprof.json 2> $O/rocprof.err < /dev/null
 f=$(find $O/rp -name "*kernel_stats.csv" 2>/dev/null | head -1); [ -n "$f" ] && cp "$f" $O/kernel_stats.csv
 rm -rf $O/rp
 fi
 if has variants; then
 VARS=("--streams 8192 --groups 3" "--streams 8192 --groups 4" "--streams 8192 --groups 5" "--streams 8192 --groups 6" "--streams 8192 --groups 8" "--streams 12288 --ring-frames 16 --groups 4" "--streams 12288 --ring-frames 16 --groups 7" "--streams 10240 --ring-frames 20 --groups 6" "--streams 6144 --groups 4" "--backend-mode 2" "--host-map" "--pre-decimated --streams 12288")
 for v in "${VARS[@]}"; do
-  echo "== $v"; timeout 600 python bench.py $v $QUIET --spread-windows 3 --super-windows 0 2>/dev/null | tail -1 | python -c "
+  echo "== $v"; timeout 600 python bench.py --full $v $QUIET --spread-windows 3 --super-windows 0 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); w = d['value_windows']; k = d['kernel_ms']
 print('value %.0f (min %.0f max %.0f) ms/step %.3f S %d G %d ring %s | kernel-ms ' % (d['value'], w['min'], w['max'], d['ms_per_step'], d['config']['streams_per_gpu'], d['config']['host_threads_per_gpu'], d['config']['frame_ring']) + ', '.join('%s %.0f' % (a, b) for a, b in k.items()) + ' | roofline %s frac %.4f' % (d['roofline']['interval'], d['roofline']['frac']))"
@@ -44,7 +44,7 @@ fi
 if has latency; then
 ( for fr in "--pre-decimated" ""; do for s in 1 8 64; do
 for v in "--backend-mode 1" "--backend-mode 2 --backend-lag 1" "--backend-mode 2 --backend-lag 6"; do
-python bench.py $fr --streams $s --groups 1 --host-threads 1 --steps 300 --warmup 20 --ring-frames 160 $QUIET --spread-windows 3 --super-windows 0 --low-latency $v 2>/dev/null | tail -1 | python -c "
+python bench.py --full $fr --streams $s --groups 1 --host-threads 1 --steps 300 --warmup 20 --ring-frames 160 $QUIET --spread-windows 3 --super-windows 0 --low-latency $v 2>/dev/null | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); h=d['host_ms_per_step']; k=d['kernel_ms']; sp=d.get('value_spread') or {}
 print('S=$s $fr $v --low-latency: fps %.0f (ms/step %.3f) with the per-family HIP events of the measurement; without them %.0f (three further windows %s)  in_abi %.3f  kernel ms/step: ' % (d['value_windows']['first'], d['value_windows']['first_ms_per_step'], sp.get('mean', 0), sp.get('windows'), h['in_abi_calls']) + ', '.join('%s %.3f' % (a, b/d['steps']) for a,b in k.items()), ' kf', d['config']['keyframes_in_timed_region'], 'ate', d['config']['checks'])"
 done; done; done ) > $O/latency_small_S.txt 2>&1
@@ -52,7 +52,7 @@ fi
 if has coop; then
 # low-latency BA through hipLaunchCooperativeKernel (SVSLAM_LL_COOP=1) against the ordinary launch: a lone camera's frame rate and the solver alone
 ( for c in 0 1 0 1; do
-SVSLAM_LL_COOP=$c python bench.py --pre-decimated --streams 1 --groups 1 --host-threads 1 --steps 300 --warmup 20 $QUIET --spread-windows 3 --super-windows 0 --low-latency --backend-mode 1 2>/dev/null | tail -1 | python -c "
+SVSLAM_LL_COOP=$c python bench.py --full --pre-decimated --streams 1 --groups 1 --host-threads 1 --steps 300 --warmup 20 $QUIET --spread-windows 3 --super-windows 0 --low-latency --backend-mode 1 2>/dev/null | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); sp=d.get('value_spread') or {}; k=d['kernel_ms']
 print('SVSLAM_LL_COOP=$c S=1 mode 1: %.0f frames/s with HIP events, %.0f without (%s); local_ba %.3f ms/step, ba_solve %.3f' % (d['value_windows']['first'], sp.get('mean', 0), sp.get('windows'), k['local_ba']/d['steps'], k['ba_solve']/d['steps']))"
 done
