@@ -179,7 +179,10 @@ int orc_gftt(const uint8_t *img, int stride, int w, int h, const float *rect_xy,
             int *nxt = (int *)malloc(sizeof(int) * (size_t)(max_corners > 0 ? max_corners : nc));
             float *acc = out_xy;
             for (int i = 0; i < gw * gh; ++i) head[i] = -1;
-            float md2 = (float)(min_dist * min_dist);
+            /* minDistance *= minDistance on the double, float operands promoted for the compare (recalled, not
+             * pinned: DESIGN section 3).  A float md2 would round a square just above an integer k onto k and keep a
+             * corner at squared distance exactly k that the double compare drops. */
+            const double md2 = min_dist * min_dist;
             for (int i = 0; i < nc; ++i) {
                 int y = cand[i].idx / w, x = cand[i].idx - y * w;
                 int xc = x / cell, yc = y / cell;
@@ -190,7 +193,7 @@ int orc_gftt(const uint8_t *img, int stride, int w, int h, const float *rect_xy,
                     for (int xx = x1; xx <= x2 && good; ++xx)
                         for (int j = head[yy * gw + xx]; j >= 0; j = nxt[j]) {
                             float dx = (float)x - acc[2 * j], dy = (float)y - acc[2 * j + 1];
-                            if (dx * dx + dy * dy < md2) { good = 0; break; }
+                            if ((double)(dx * dx + dy * dy) < md2) { good = 0; break; }
                         }
                 if (good) {
                     acc[2 * ncorners] = (float)x; acc[2 * ncorners + 1] = (float)y;

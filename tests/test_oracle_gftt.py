@@ -3,30 +3,7 @@ of the declared operation order, and against the defining properties of the dete
 import numpy as np
 
 import common as cm
-
-
-def _eig_numpy(img):
-    f = np.float32
-    p = np.pad(img.astype(np.float32), 1, mode="reflect")
-    s1 = f(1.0 / 3060.0); s2 = f(2.0 * (1.0 / 3060.0))
-    c = lambda dy, dx: p[1 + dy:p.shape[0] - 1 + dy, 1 + dx:p.shape[1] - 1 + dx]
-    d0 = c(-1, 1) - c(-1, -1); d1 = c(0, 1) - c(0, -1); d2 = c(1, 1) - c(1, -1)
-    Dx = (d0 + d2) * s1 + d1 * s2
-    c0 = (s1 * c(-1, -1) + s2 * c(-1, 0)) + s1 * c(-1, 1)
-    c2 = (s1 * c(1, -1) + s2 * c(1, 0)) + s1 * c(1, 1)
-    Dy = c2 - c0
-    assert Dx.dtype == np.float32 and Dy.dtype == np.float32
-    out = []
-    for m in (Dx * Dx, Dx * Dy, Dy * Dy):
-        q = np.pad(m, 1, mode="reflect").astype(np.float64)
-        s = np.zeros_like(m, dtype=np.float64)
-        for j in range(3):           # same accumulation order as the oracle (rows outer)
-            for i in range(3):
-                s = s + q[j:j + m.shape[0], i:i + m.shape[1]]
-        out.append(s.astype(np.float32))
-    a = out[0] * f(0.5); b = out[1]; cc = out[2] * f(0.5)
-    t = a - cc
-    return (a + cc) - np.sqrt(t * t + b * b)
+from ref_frontend import _eig_numpy, _greedy_python
 
 
 def test_min_eig_map_bit_exact_vs_numpy(orc):
@@ -46,32 +23,6 @@ def test_mask_rounding_half_even_inclusive_clipped(orc):
     assert m[0:11, 0:11].max() == 0            # clipped square around (0,0): [-10,10] -> [0,10]
     assert m[37:48, 53:64].max() == 0
     assert m[30, 40] == 255
-
-
-def _greedy_python(eig, mask, max_corners, quality, min_dist):
-    h, w = eig.shape
-    mx = eig[mask > 0].max() if (mask > 0).any() else 0.0
-    thr = np.float32(float(mx) * quality)
-    cand = []
-    for y in range(1, h - 1):
-        for x in range(1, w - 1):
-            v = eig[y, x]
-            if not (v > thr) or v == 0 or not mask[y, x]:
-                continue
-            nb = eig[y - 1:y + 2, x - 1:x + 2]
-            if (np.where(nb > thr, nb, 0) > v).any():
-                continue
-            cand.append((float(v), y * w + x))
-    cand.sort(key=lambda t: (-t[0], -t[1]))
-    acc = []
-    for v, idx in cand:
-        y, x = divmod(idx, w)
-        if min_dist >= 1 and any((x - ax) ** 2 + (y - ay) ** 2 < min_dist * min_dist for ax, ay in acc):
-            continue
-        acc.append((x, y))
-        if len(acc) == max_corners:
-            break
-    return np.array(acc, np.float32).reshape(-1, 2)
 
 
 def test_gftt_matches_python_selection(orc):

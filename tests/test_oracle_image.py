@@ -6,6 +6,7 @@ import pytest
 from scipy import ndimage
 
 import common as cm
+from ref_frontend import _ref_lk_single_level
 
 
 def test_pyrdown_matches_scipy_mirror(orc):
@@ -47,74 +48,6 @@ def test_decimate_is_even_sampling(orc):
     dec = orc.decimate(full)
     assert dec.shape == (188, 620)            # cvRound(620.5) = 620 (half to even), SURVEY F3
     assert np.array_equal(dec, full[0:376:2, 0:1240:2])
-
-
-def _ref_lk_single_level(I, J, pts, guess, max_iter=30, eps=0.01, win=11):
-    """independent numpy restatement of one LK level (OpenCV LKTrackerInvoker, level 0 only,
-    float accumulators exactly like the scalar C++ code)"""
-    W_BITS = 14
-    h, w = I.shape
-    B = win
-    Ib = np.pad(I.astype(np.int64), B, mode="reflect")
-    Jb = np.pad(J.astype(np.int64), B, mode="reflect")
-    a = I.astype(np.int64)
-    sm = np.array([3, 10, 3]); df = np.array([-1, 0, 1])
-    dx = ndimage.correlate1d(ndimage.correlate1d(a, sm, axis=0, mode="mirror"), df, axis=1, mode="mirror")
-    dy = ndimage.correlate1d(ndimage.correlate1d(a, df, axis=0, mode="mirror"), sm, axis=1, mode="mirror")
-    dxb = np.pad(dx, B); dyb = np.pad(dy, B)
-    half = np.float32((win - 1) * 0.5)
-    out = guess.astype(np.float32).copy(); status = np.ones(len(pts), np.uint8)
-
-    def weights(fx, fy):
-        ix, iy = int(np.floor(fx)), int(np.floor(fy))
-        a_ = np.float32(fx - np.float32(ix)); b_ = np.float32(fy - np.float32(iy))
-        one = np.float32(1)
-        w00 = int(np.rint(np.float32(np.float32((one - a_) * (one - b_)) * np.float32(1 << W_BITS))))
-        w01 = int(np.rint(np.float32(np.float32(a_ * (one - b_)) * np.float32(1 << W_BITS))))
-        w10 = int(np.rint(np.float32(np.float32((one - a_) * b_) * np.float32(1 << W_BITS))))
-        return ix, iy, w00, w01, w10, (1 << W_BITS) - w00 - w01 - w10
-
-    def patch(img_b, ix, iy, ws, shift):
-        y0, x0 = iy + B, ix + B
-        p = img_b[y0:y0 + win + 1, x0:x0 + win + 1]
-        v = p[:-1, :-1] * ws[0] + p[:-1, 1:] * ws[1] + p[1:, :-1] * ws[2] + p[1:, 1:] * ws[3]
-        return (v + (1 << (shift - 1))) >> shift
-
-    for n, (p, g) in enumerate(zip(pts.astype(np.float32), guess.astype(np.float32))):
-        px, py = np.float32(p[0] - half), np.float32(p[1] - half)
-        ix, iy, *ws = weights(px, py)
-        if ix < -win or ix >= w or iy < -win or iy >= h:
-            status[n] = 0
-            continue
-        Iw = patch(Ib, ix, iy, ws, W_BITS - 5); Ix = patch(dxb, ix, iy, ws, W_BITS); Iy = patch(dyb, ix, iy, ws, W_BITS)
-        sc = np.float32(1.0 / (1 << 20))
-        A11 = np.float32(np.float32((Ix * Ix).sum()) * sc); A12 = np.float32(np.float32((Ix * Iy).sum()) * sc)
-        A22 = np.float32(np.float32((Iy * Iy).sum()) * sc)
-        D = np.float32(A11 * A22 - A12 * A12)
-        mine = (A22 + A11 - np.sqrt(np.float32((A11 - A22) ** 2 + np.float32(4) * A12 * A12))) / np.float32(2 * win * win)
-        if mine < 1e-4 or D < np.finfo(np.float32).eps:
-            status[n] = 0
-            continue
-        D = np.float32(1) / D
-        nx, ny = np.float32(g[0] - half), np.float32(g[1] - half)
-        pdx = pdy = np.float32(0)
-        for j in range(max_iter):
-            jx, jy, *wj = weights(nx, ny)
-            if jx < -win or jx >= w or jy < -win or jy >= h:
-                status[n] = 0
-                break
-            diff = patch(Jb, jx, jy, wj, W_BITS - 5) - Iw
-            b1 = np.float32(np.float32((diff * Ix).sum()) * sc); b2 = np.float32(np.float32((diff * Iy).sum()) * sc)
-            ddx = np.float32(np.float32(A12 * b2 - A22 * b1) * D); ddy = np.float32(np.float32(A12 * b1 - A11 * b2) * D)
-            nx = np.float32(nx + ddx); ny = np.float32(ny + ddy)
-            out[n] = (nx + half, ny + half)
-            if float(ddx) ** 2 + float(ddy) ** 2 <= eps * eps:
-                break
-            if j > 0 and abs(float(ddx + pdx)) < 0.01 and abs(float(ddy + pdy)) < 0.01:
-                out[n] -= np.array([ddx, ddy], np.float32) * np.float32(0.5)
-                break
-            pdx, pdy = ddx, ddy
-    return out, status
 
 
 def test_lk_level0_matches_independent_numpy(orc):
