@@ -1610,8 +1610,11 @@ k_local_ba_t(BaDev *jobs, const BaCams *camsp, double *poses_all, double *pts_al
                     }
                     d_se3_exp(x6, dT);
                     d_se3_mul(dT, pcur + 7 * k, Tn);
+                    // MODE 2 keeps every keyframe active: one without edges gets the step 0, and must keep its bits like the
+                    // inactive pose it is in the batch kernel and the oracle (d_se3_mul re-normalises the quaternion)
+                    const bool still = MODE == 2 && x6[0] == 0 && x6[1] == 0 && x6[2] == 0 && x6[3] == 0 && x6[4] == 0 && x6[5] == 0;
 #pragma unroll
-                    for (int t = 0; t < 7; ++t) ptrial[7 * k + t] = Tn[t];
+                    for (int t = 0; t < 7; ++t) ptrial[7 * k + t] = still ? pcur[7 * k + t] : Tn[t];
                 }
             }
             double scale = block_sum(scale_part, red, tid);

@@ -437,8 +437,11 @@ k_ba_ll(BaDev *shards, const BaCams *camsp, double *poses_all, double *pts_all, 
                     for (int t = 0; t < 6; ++t) { x6[t] = xp[6 * a + t]; scale_pose_part += x6[t] * (lambda * x6[t] + bpt[6 * a + t]); }   // every shard computes the same
                     d_se3_exp(x6, dT);
                     d_se3_mul(dT, Pc + 7 * k, Tn);
+                    // a keyframe without edges (active here like every keyframe) gets the step 0: it keeps its bits, like the
+                    // inactive pose it is in the batch kernel and the oracle (d_se3_mul re-normalises the quaternion)
+                    const bool still = x6[0] == 0 && x6[1] == 0 && x6[2] == 0 && x6[3] == 0 && x6[4] == 0 && x6[5] == 0;
 #pragma unroll
-                    for (int t = 0; t < 7; ++t) Pt[7 * k + t] = Tn[t];
+                    for (int t = 0; t < 7; ++t) Pt[7 * k + t] = still ? Pc[7 * k + t] : Tn[t];
                 }
                 BA_PROF(5);
                 // the trial state: its chi2 — and, if it is accepted, the next trial's linearisation
