@@ -161,6 +161,55 @@ int svslam_gftt_batch(svslam_ctx *ctx, int njobs, const svslam_gftt_job *jobs,
 /* test hook: min-eigenvalue map of a slot's level-0 image (w*h floats) */
 int svslam_gftt_eigmap(svslam_ctx *ctx, int slot, float *out);
 
+/* ---- dense stereo: the reference's second program (run_dense_reconstruction) ---------------
+ * svslam_stereo_bm_batch replaces stereo_depth_est_->compute(left, right, disparity_map) at
+ * src/dense_reconstruction.cpp:114 (matcher created at :89 as cv::StereoBM::create(128, 15),
+ * include/StereoVisionSLAM/dense_reconstruction.h:56-57; everything else at OpenCV's defaults:
+ * PREFILTER_XSOBEL, minDisparity 0, no speckle filter, no disp12MaxDiff).  The images are level 0
+ * of two pyramid slots.  Output: CV_16S maps of 16 x disparity, -16 where OpenCV writes none.
+ * An image too small for one window (nd - 1 + r >= w - r, or h < 2 r + 1 with r = block_size / 2)
+ * succeeds with every pixel -16, like OpenCV.
+ * num_disparities: positive multiple of 16, <= 256; block_size: odd, 5 .. 21; pre_filter_cap: 1 .. 63.
+ * Colour input, PREFILTER_NORMALIZED_RESPONSE, the speckle filter and disp12MaxDiff are not built.  */
+typedef struct svslam_bm_params {
+    int num_disparities;   /* 128 */
+    int block_size;        /* 15  */
+    int pre_filter_cap;    /* 31  */
+    int texture_threshold; /* 10  */
+    int uniqueness_ratio;  /* 15  */
+    int reserved;
+} svslam_bm_params;
+typedef struct svslam_bm_job { int slot_left, slot_right; } svslam_bm_job;   /* level 0 of each pyramid slot */
+
+int svslam_stereo_bm_batch(svslam_ctx *ctx, int njobs, const svslam_bm_job *jobs, const svslam_bm_params *p,
+                           int16_t *out_disp /* [njobs][height][width] */);
+
+/* test hook: the output rows per workgroup strip (16, 8 or 4, by the number of workgroups the call has) that a
+ * call of njobs jobs with these parameters runs with; 0 where the image is too small for one window.  The
+ * result of the matcher does not depend on it; the tests use it to know that they cover every strip height. */
+int svslam_stereo_bm_strip_rows(svslam_ctx *ctx, int njobs, const svslam_bm_params *p);
+
+/* The matcher followed by the loop of src/dense_reconstruction.cpp:116-173 with its types: disparity
+ * x 1/16 in float, depth = (float fx * float baseline) / disparity (0 where disparity <= 0), pixels with
+ * depth < min_depth (1 in the reference) dropped, the rest through Camera::pixel2world (src/camera.cpp:
+ * 39-44, 58-86: T_cw^-1 * ext_l^-1 * pixel2camera) in double and rounded to float (PointXYZRGB).
+ * Job i's points are written from out_xyz[3 * pt_ofs] / out_pix[pt_ofs] on in the reference's order —
+ * x outer, y inner; out_pix holds y * width + x of each point, for the caller to colour it from the
+ * image it holds.  n_points (out) beyond max_pts_per_job is an error, nothing of that call is returned.
+ * out_disp_or_null: the disparity maps as svslam_stereo_bm_batch returns them.
+ * Not built: StatisticalOutlierRemoval and the VoxelGrid of :175-209 (PCL).                        */
+typedef struct svslam_dense_job {
+    int    slot_left, slot_right;
+    int    pt_ofs;         /* in: where this job's points start in out_xyz / out_pix */
+    int    n_points;       /* out                                                     */
+    double T_cw[7];        /* keyframe pose (keyframes_poses_[i].cast<double>())      */
+} svslam_dense_job;
+
+int svslam_dense_cloud_batch(svslam_ctx *ctx, int njobs, svslam_dense_job *jobs, const double cam_l[4],
+                             const double ext_l[7], double baseline, const svslam_bm_params *p,
+                             double min_depth, int max_pts_per_job, float *out_xyz, int *out_pix,
+                             int16_t *out_disp_or_null);
+
 /* ---- stereo triangulation ----------------------------------------------
  * Replaces slam::triangulation() (include/StereoVisionSLAM/algorithm.h:10-87)
  * as called from BuildInitMap (src/frontend.cpp:165-174) and
@@ -436,7 +485,10 @@ int svslam_sync(svslam_ctx *ctx);
 /* ---- kernel timing (HIP events on the context's stream) -------------------
  * Accumulated per kernel family since the last reset; used by bench.py for
  * the roofline entry.  family: 0 pyramid, 1 lk, 2 gftt, 3 triangulate,
- * 4 pose_only, 5 local_ba.                                                   */
+ * 4 pose_only, 5 local_ba, 6 stereo_bm (units = jobs).
+ * Development families follow and are NOT stable numbers: with stereo_bm taking 6, the
+ * per-kernel split moved from 6-9 to 7-10 and the local-BA solver interval from 10 to 11.
+ * A caller that passed those raw numbers must move with them (Python addresses them by name). */
 int svslam_timing_enable(svslam_ctx *ctx, int on);
 int svslam_timing_reset(svslam_ctx *ctx);
 int svslam_timing_get(svslam_ctx *ctx, int family, double *total_ms,

@@ -19,7 +19,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 ABI_SYMBOLS = [
     "svslam_create", "svslam_destroy", "svslam_last_error", "svslam_build_info",
     "svslam_pyramid_batch", "svslam_pyramid_decimate_batch", "svslam_set_source_size", "svslam_set_low_latency", "svslam_set_pose_only_xtol", "svslam_get_pose_only_xtol", "svslam_pyramid_read",
-    "svslam_pyramid_read_padded", "svslam_lk_batch", "svslam_gftt_batch", "svslam_gftt_eigmap", "svslam_triangulate_batch",
+    "svslam_pyramid_read_padded", "svslam_stereo_bm_batch", "svslam_stereo_bm_strip_rows", "svslam_dense_cloud_batch", "svslam_lk_batch", "svslam_gftt_batch", "svslam_gftt_eigmap", "svslam_triangulate_batch",
     "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect",
     "svslam_track_batch", "svslam_rtrack_batch", "svslam_rtrack_upload",
     "svslam_sba_io_doubles", "svslam_sba_open", "svslam_sba_phase", "svslam_sba_close",
@@ -30,14 +30,15 @@ ABI_SYMBOLS = [
 ]
 
 FAMILIES = {"pyramid": 0, "lk": 1, "gftt": 2, "triangulate": 3, "pose_only": 4, "local_ba": 5}
-DEBUG_FAMILIES = {"dbg0": 6, "dbg1": 7, "dbg2": 8, "dbg3": 9}     # per-kernel split (SVSLAM_TIMING_SPLIT=1), development
+DENSE_FAMILIES = {"stereo_bm": 6}      # the dense-reconstruction program's kernels: not part of the per-frame loop bench.py sums over FAMILIES
+DEBUG_FAMILIES = {"dbg0": 7, "dbg1": 8, "dbg2": 9, "dbg3": 10}     # per-kernel split (SVSLAM_TIMING_SPLIT=1), development
 # intervals nested inside a family: the local-BA solver kernel alone (k_local_ba_t<0, 1, EID>, or the low-latency solver's kernels)
 # inside "local_ba" (= map gather + structure build + solver + scatter)
-KERNEL_FAMILIES = {"ba_solve": 10}
+KERNEL_FAMILIES = {"ba_solve": 11}
 # the HIP kernel(s) behind each timing family at the batch operating point (what a rocprofv3 --kernel-trace --stats row is named)
 FAMILY_KERNELS = {"pyramid": ["k_pyr_fused"], "lk": ["k_lk"], "gftt": ["k_gftt_eig3", "k_gftt_select2"], "triangulate": ["k_triangulate"],
                   "pose_only": ["k_pose_only"], "local_ba": ["k_dmap_ba_gather", "k_ba_build", "k_local_ba_t", "k_dmap_ba_scatter"],
-                  "ba_solve": ["k_local_ba_t"]}
+                  "ba_solve": ["k_local_ba_t"], "stereo_bm": ["k_bm_fill", "k_stereo_bm", "k_dense_cloud"]}
 
 
 class Limits(C.Structure):
@@ -77,6 +78,20 @@ class PoseJob(C.Structure):
 class BaJob(C.Structure):
     _fields_ = [("kf_ofs", C.c_int), ("nkf", C.c_int), ("lm_ofs", C.c_int), ("nlm", C.c_int),
                 ("obs_ofs", C.c_int), ("nobs", C.c_int), ("iters_done", C.c_int), ("reserved", C.c_int)]
+
+
+class BmParams(C.Structure):
+    _fields_ = [("num_disparities", C.c_int), ("block_size", C.c_int), ("pre_filter_cap", C.c_int),
+                ("texture_threshold", C.c_int), ("uniqueness_ratio", C.c_int), ("reserved", C.c_int)]
+
+
+class BmJob(C.Structure):
+    _fields_ = [("slot_left", C.c_int), ("slot_right", C.c_int)]
+
+
+class DenseJob(C.Structure):
+    _fields_ = [("slot_left", C.c_int), ("slot_right", C.c_int), ("pt_ofs", C.c_int), ("n_points", C.c_int),
+                ("T_cw", C.c_double * 7)]
 
 
 class TrackJob(C.Structure):
@@ -249,7 +264,7 @@ class Context:
 
     def timing_get(self, family):
         ms, n, u = C.c_double(), C.c_longlong(), C.c_longlong()
-        fam = FAMILIES[family] if family in FAMILIES else (KERNEL_FAMILIES[family] if family in KERNEL_FAMILIES else DEBUG_FAMILIES[family])
+        fam = next(t[family] for t in (FAMILIES, KERNEL_FAMILIES, DENSE_FAMILIES, DEBUG_FAMILIES) if family in t)
         self._chk(self.L.svslam_timing_get(self.h, fam, C.byref(ms), C.byref(n), C.byref(u)), "timing")
         return ms.value, n.value, u.value
 
@@ -300,6 +315,47 @@ class Context:
         out = np.zeros((h.value + 32, w.value + 32), np.uint8)
         self._chk(self.L.svslam_pyramid_read_padded(self.h, slot, level, _p(out)), "pyramid_read_padded")
         return out
+
+    # ---- dense stereo ----------------------------------------------------
+    @staticmethod
+    def _bm_params(num_disparities=128, block_size=15, pre_filter_cap=31, texture_threshold=10, uniqueness_ratio=15):
+        return BmParams(num_disparities, block_size, pre_filter_cap, texture_threshold, uniqueness_ratio, 0)
+
+    def stereo_bm(self, jobs, **params):
+        """cv::StereoBM on level 0 of pyramid slots.  jobs: list of (slot_left, slot_right); params: num_disparities 128,
+        block_size 15, pre_filter_cap 31, texture_threshold 10, uniqueness_ratio 15.  returns int16 [njobs, h, w] of
+        16 x disparity, -16 where there is none."""
+        n = len(jobs)
+        arr = (BmJob * max(n, 1))(*[BmJob(int(l), int(r)) for l, r in jobs])
+        out = np.zeros((n, self.height, self.width), np.int16)
+        prm = self._bm_params(**params)
+        self._chk(self.L.svslam_stereo_bm_batch(self.h, n, arr, C.byref(prm), _p(out)), "stereo_bm_batch")
+        return out
+
+    def stereo_bm_strip_rows(self, njobs, **params):
+        """test hook: the strip height (16, 8 or 4 output rows per workgroup; 0 on the early-out) a call of njobs jobs runs with"""
+        prm = self._bm_params(**params)
+        th = self.L.svslam_stereo_bm_strip_rows(self.h, int(njobs), C.byref(prm))
+        if th < 0:
+            self._chk(th, "stereo_bm_strip_rows")
+        return th
+
+    def dense_cloud(self, jobs, cam_l, ext_l, baseline, min_depth=1.0, max_pts_per_job=None, **params):
+        """the matcher + src/dense_reconstruction.cpp:116-173.  jobs: list of (slot_left, slot_right, T_cw[7] or None).
+        returns per job (xyz float32 [n, 3] in the map frame, pix int32 [n] = y * width + x, disp int16 [h, w]), the
+        points in the reference's order (x outer, y inner)."""
+        n = len(jobs)
+        cap = self.width * self.height if max_pts_per_job is None else int(max_pts_per_job)
+        arr = (DenseJob * max(n, 1))()
+        for i, (sl, sr, T) in enumerate(jobs):
+            arr[i] = DenseJob(int(sl), int(sr), i * cap, 0, (C.c_double * 7)(*(IDENT if T is None else _d(T))))
+        xyz = np.zeros((max(n * cap, 1), 3), np.float32); pix = np.zeros(max(n * cap, 1), np.int32)
+        disp = np.zeros((n, self.height, self.width), np.int16)
+        prm = self._bm_params(**params)
+        self._chk(self.L.svslam_dense_cloud_batch(self.h, n, arr, _p(_d(cam_l)), _p(_d(ext_l)), C.c_double(baseline), C.byref(prm),
+                                                  C.c_double(min_depth), cap, _p(xyz), _p(pix), _p(disp)), "dense_cloud_batch")
+        return [(xyz[j.pt_ofs:j.pt_ofs + j.n_points].copy(), pix[j.pt_ofs:j.pt_ofs + j.n_points].copy(), disp[i].copy())
+                for i, j in enumerate(arr[:n])]
 
     # ---- LK --------------------------------------------------------------
     def lk(self, jobs, params=None):

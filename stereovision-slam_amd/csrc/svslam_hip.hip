@@ -42,6 +42,7 @@ typedef enum { ncclDouble = 8 } ncclDataType_t;
 #include "k_ba_build.h"
 #include "k_ba_ll.h"
 #include "k_dmap.h"
+#include "k_stereo_bm.h"
 
 #define SVSLAM_DMAP_CHUNK 512     /* keyframe jobs per svslam_dmap_keyframe_batch call the staging arena is sized for */
 #define SVSLAM_DMAP_EVICT_PER_JOB 512   /* evicted-landmark records per job of a call (shared by the call's jobs; the surplus waits) */
@@ -49,8 +50,10 @@ typedef enum { ncclDouble = 8 } ncclDataType_t;
 
 namespace {
 
-enum { FAM_PYR = 0, FAM_LK, FAM_GFTT, FAM_TRI, FAM_POSE, FAM_BA, FAM_DBG0, FAM_DBG1, FAM_DBG2, FAM_DBG3,
-       FAM_BA_SOLVE,   // the local-BA solver kernel(s) alone, nested inside FAM_BA (gather + build + solve + scatter)
+enum { FAM_PYR = 0, FAM_LK, FAM_GFTT, FAM_TRI, FAM_POSE, FAM_BA,
+       FAM_BM,         // family 6 of svslam_timing_get: the dense-stereo kernels (k_bm_fill + k_stereo_bm [+ k_dense_cloud])
+       FAM_DBG0, FAM_DBG1, FAM_DBG2, FAM_DBG3,      // development (SVSLAM_TIMING_SPLIT): 7 .. 10
+       FAM_BA_SOLVE,   // 11: the local-BA solver kernel(s) alone, nested inside FAM_BA (gather + build + solve + scatter)
        FAM_COUNT };
 
 struct Timing {
@@ -92,6 +95,8 @@ struct svslam_ctx {
     size_t h_img_cap = 0;
     // GFTT scratch
     GfttWork gw;
+    // dense stereo scratch (svslam_stereo_bm_batch / svslam_dense_cloud_batch), allocated at first use for max_jobs images
+    struct { int16_t *disp = nullptr; float *xyz = nullptr; int *pix = nullptr; } bm;
     // BA scratch
     BaWork bw;
     int bw_jobs = 0;          // problems per call the BA scratch holds
@@ -755,6 +760,7 @@ void svslam_destroy(svslam_ctx *c)
         (void)hipFree(c->gw.prof);
     }
     (void)hipFree(c->gw.keys); (void)hipFree(c->gw.counters);
+    (void)hipFree(c->bm.disp); (void)hipFree(c->bm.xyz); (void)hipFree(c->bm.pix);
     ba_work_free(c->bw);
     ll_release(c);
     if (c->d_ba_prof) (void)hipFree(c->d_ba_prof);
@@ -1096,6 +1102,147 @@ int svslam_gftt_eigmap(svslam_ctx *c, int slot, float *out)
     hipError_t e4 = hipMemcpy(out, d_eig, sizeof(float) * (size_t)w * h, hipMemcpyDeviceToHost);
     (void)hipFree(d_eig);
     HIPCHK(c, e1); HIPCHK(c, e2); HIPCHK(c, e3); HIPCHK(c, e4);
+    return 0;
+}
+
+// ------------------------------------------------------------------ dense stereo (run_dense_reconstruction)
+static int bm_check_params(svslam_ctx *c, const svslam_bm_params *p, BmParams &P)
+{
+    if (!p) return fail(c, "stereo_bm: null parameters");
+    if (p->num_disparities <= 0 || (p->num_disparities & 15) || p->num_disparities > 256)
+        return fail(c, "stereo_bm: num_disparities %d must be a positive multiple of 16, <= 256", p->num_disparities);
+    if (!(p->block_size & 1) || p->block_size < 5 || p->block_size > 21) return fail(c, "stereo_bm: block_size %d must be odd and in [5, 21]", p->block_size);
+    if (p->pre_filter_cap < 1 || p->pre_filter_cap > 63) return fail(c, "stereo_bm: pre_filter_cap %d out of [1, 63]", p->pre_filter_cap);
+    if (p->texture_threshold < 0 || p->uniqueness_ratio < 0) return fail(c, "stereo_bm: texture_threshold %d / uniqueness_ratio %d must not be negative", p->texture_threshold, p->uniqueness_ratio);
+    // (uniqueness_ratio stays an int product: minsad <= 21 * 21 * 126)
+    if (p->uniqueness_ratio > 10000) return fail(c, "stereo_bm: uniqueness_ratio %d > 10000", p->uniqueness_ratio);
+    P.nd = p->num_disparities; P.bs = p->block_size; P.cap = p->pre_filter_cap; P.tex_thr = p->texture_threshold; P.uniq = p->uniqueness_ratio;
+    return 0;
+}
+
+// rows per strip of k_stereo_bm: 16 amortise the 2r+1 rows a strip starts with; a call of few jobs takes shorter strips (8, 4) to
+// fill the device.  0 on stereobm.cpp's early-out (no column or no row to compute: every pixel FILTERED)
+static int bm_strip_rows(int w, int h, int njobs, const BmParams &P)
+{
+    const int r = P.bs / 2, x0 = P.nd - 1 + r, x1 = w - r, y0 = r, y1 = h - r;
+    if (x0 >= x1 || h < 2 * r + 1) return 0;
+    const int tiles = cdiv(x1 - x0, BM_TW);
+    int th = 16;
+    while (th > 4 && (long long)tiles * cdiv(y1 - y0, th) * njobs < 1024) th >>= 1;
+    return th;
+}
+
+int svslam_stereo_bm_strip_rows(svslam_ctx *c, int njobs, const svslam_bm_params *p)
+{
+    if (!c) return -1;
+    BmParams P;
+    if (bm_check_params(c, p, P)) return -1;
+    if (njobs <= 0 || njobs > c->lim.max_jobs) return fail(c, "stereo_bm: %d jobs out of [1, max_jobs]", njobs);
+    return bm_strip_rows(c->geom.w[0], c->geom.h[0], njobs, P);
+}
+
+// enqueue the matcher for njobs jobs (device array djobs) into c->bm.disp; no-op arithmetic when OpenCV's early-out applies
+static int launch_stereo_bm(svslam_ctx *c, int njobs, const BmJob *djobs, const BmParams &P)
+{
+    const int w = c->geom.w[0], h = c->geom.h[0], r = P.bs / 2;
+    if (!c->bm.disp) HIPCHK(c, hipMalloc(&c->bm.disp, sizeof(int16_t) * (size_t)w * h * c->lim.max_jobs));
+    const int x0 = P.nd - 1 + r, x1 = w - r, y0 = r, y1 = h - r;
+    const int th = bm_strip_rows(w, h, njobs, P);
+    const bool none = th == 0;
+    const size_t n = (size_t)w * h * njobs;
+    hipLaunchKernelGGL(k_bm_fill, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->stream, c->bm.disp, w, h, njobs,
+                       none ? 0 : x0, none ? 0 : x1, none ? 0 : y0, none ? 0 : y1);
+    if (!none) {
+        const dim3 grid(cdiv(x1 - x0, BM_TW), cdiv(y1 - y0, th), njobs);
+        const size_t lds = bm_lds_bytes(P.nd, P.bs, th);
+        switch ((P.bs + 3) / 4) {
+        case 2: hipLaunchKernelGGL(k_stereo_bm<2>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
+        case 3: hipLaunchKernelGGL(k_stereo_bm<3>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
+        case 4: hipLaunchKernelGGL(k_stereo_bm<4>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
+        case 5: hipLaunchKernelGGL(k_stereo_bm<5>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
+        default: hipLaunchKernelGGL(k_stereo_bm<6>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+int svslam_stereo_bm_batch(svslam_ctx *c, int njobs, const svslam_bm_job *jobs, const svslam_bm_params *p, int16_t *out_disp)
+{
+    if (!c) return -1;
+    BmParams P;
+    if (bm_check_params(c, p, P)) return -1;
+    if (njobs <= 0) return 0;
+    if (njobs > c->lim.max_jobs) return fail(c, "stereo_bm: %d jobs > max_jobs", njobs);
+    if (!jobs || !out_disp) return fail(c, "stereo_bm: null jobs / output");
+    for (int i = 0; i < njobs; ++i) if (check_slot(c, jobs[i].slot_left) || check_slot(c, jobs[i].slot_right)) return -1;
+    if (arena_busy(c)) return -1;
+    c->ar.reset();
+    static_assert(sizeof(BmJob) == sizeof(svslam_bm_job), "job layout");
+    const size_t ojobs = c->ar.take(sizeof(BmJob) * njobs);
+    memcpy(hp<void>(c, ojobs), jobs, sizeof(BmJob) * njobs);
+    if (h2d(c, 0, c->ar.off)) return -1;
+    tm_begin(c, FAM_BM, njobs);
+    const int rc = launch_stereo_bm(c, njobs, dp<BmJob>(c, ojobs), P);
+    tm_end(c);
+    if (rc) return -1;
+    HIPCHK(c, hipMemcpyAsync(out_disp, c->bm.disp, sizeof(int16_t) * (size_t)c->geom.w[0] * c->geom.h[0] * njobs, hipMemcpyDeviceToHost, c->stream));
+    if (d2h_sync(c, 0, 0)) return -1;
+    return 0;
+}
+
+int svslam_dense_cloud_batch(svslam_ctx *c, int njobs, svslam_dense_job *jobs, const double cam_l[4], const double ext_l[7], double baseline,
+                             const svslam_bm_params *p, double min_depth, int max_pts_per_job, float *out_xyz, int *out_pix,
+                             int16_t *out_disp_or_null)
+{
+    if (!c) return -1;
+    BmParams P;
+    if (bm_check_params(c, p, P)) return -1;
+    if (njobs <= 0) return 0;
+    if (njobs > c->lim.max_jobs) return fail(c, "dense_cloud: %d jobs > max_jobs", njobs);
+    if (!jobs || !cam_l || !ext_l || !out_xyz || !out_pix) return fail(c, "dense_cloud: null argument");
+    if (max_pts_per_job < 1) return fail(c, "dense_cloud: max_pts_per_job %d < 1", max_pts_per_job);
+    if (!(cam_l[0] > 0) || !(cam_l[1] > 0) || !(baseline > 0) || !(min_depth > 0)) return fail(c, "dense_cloud: fx, fy, baseline and min_depth must be positive");
+    for (int i = 0; i < njobs; ++i) {
+        if (check_slot(c, jobs[i].slot_left) || check_slot(c, jobs[i].slot_right)) return -1;
+        if (jobs[i].pt_ofs < 0) return fail(c, "dense_cloud: job %d: negative pt_ofs", i);
+    }
+    if (arena_busy(c)) return -1;
+    const int w = c->geom.w[0], h = c->geom.h[0];
+    const size_t N = (size_t)w * h;
+    const int cap = (int)std::min<size_t>((size_t)max_pts_per_job, N);     // a job has at most w h survivors
+    if (!c->bm.xyz) HIPCHK(c, hipMalloc(&c->bm.xyz, sizeof(float) * 3 * N * c->lim.max_jobs));
+    if (!c->bm.pix) HIPCHK(c, hipMalloc(&c->bm.pix, sizeof(int) * N * c->lim.max_jobs));
+    c->ar.reset();
+    static_assert(sizeof(DenseJob) == sizeof(svslam_dense_job), "job layout");
+    const size_t obm = c->ar.take(sizeof(BmJob) * njobs);
+    const size_t oj = c->ar.take(sizeof(DenseJob) * njobs);
+    for (int i = 0; i < njobs; ++i) { hp<BmJob>(c, obm)[i].slot_left = jobs[i].slot_left; hp<BmJob>(c, obm)[i].slot_right = jobs[i].slot_right; }
+    memcpy(hp<void>(c, oj), jobs, sizeof(DenseJob) * njobs);
+    if (h2d(c, 0, c->ar.off)) return -1;
+    DenseCam cam;
+    cam.fx = cam_l[0]; cam.fy = cam_l[1]; cam.cx = cam_l[2]; cam.cy = cam_l[3];
+    memcpy(cam.ext, ext_l, 56);
+    cam.min_depth = min_depth;
+    cam.fxb = (float)cam_l[0] * (float)baseline;       // focal_length * baseline, both float (src/dense_reconstruction.cpp:120-124, 135)
+    tm_begin(c, FAM_BM, njobs);
+    const int rc = launch_stereo_bm(c, njobs, dp<BmJob>(c, obm), P);
+    if (!rc) hipLaunchKernelGGL(k_dense_cloud, dim3(njobs), dim3(DC_THREADS), 0, c->stream, dp<DenseJob>(c, oj), c->bm.disp, w, h, cam, cap, c->bm.xyz, c->bm.pix);
+    tm_end(c);
+    if (rc) return -1;
+    HIPCHK(c, hipGetLastError());
+    if (d2h_sync(c, oj, oj + sizeof(DenseJob) * njobs)) return -1;
+    for (int i = 0; i < njobs; ++i) {
+        jobs[i].n_points = hp<DenseJob>(c, oj)[i].n_points;
+        if (jobs[i].n_points > max_pts_per_job) return fail(c, "dense_cloud: job %d has %d points > max_pts_per_job %d", i, jobs[i].n_points, max_pts_per_job);
+    }
+    for (int i = 0; i < njobs; ++i) {
+        const size_t n = (size_t)jobs[i].n_points;
+        if (!n) continue;
+        HIPCHK(c, hipMemcpy(out_xyz + 3 * (size_t)jobs[i].pt_ofs, c->bm.xyz + 3 * (size_t)i * cap, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(out_pix + (size_t)jobs[i].pt_ofs, c->bm.pix + (size_t)i * cap, sizeof(int) * n, hipMemcpyDeviceToHost));
+    }
+    if (out_disp_or_null) HIPCHK(c, hipMemcpy(out_disp_or_null, c->bm.disp, sizeof(int16_t) * N * njobs, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -63,6 +63,14 @@ public:
 
     int pyramid(int n, const int *slots, const void *const *imgs, const int *strides, int is_device)
     { return svslam_pyramid_batch(ctx_, n, slots, imgs, strides, is_device); }
+    int pyramid_decimate(int n, const int *slots, const void *const *imgs, const int *strides, int src_w, int src_h, int is_device)
+    { return svslam_pyramid_decimate_batch(ctx_, n, slots, imgs, strides, src_w, src_h, is_device); }
+    // dense reconstruction (src/dense_reconstruction.cpp:114, :116-173)
+    int stereo_bm(int n, const svslam_bm_job *jobs, const svslam_bm_params *p, int16_t *out_disp)
+    { return svslam_stereo_bm_batch(ctx_, n, jobs, p, out_disp); }
+    int dense_cloud(int n, svslam_dense_job *jobs, const double *cam_l, const double *ext_l, double baseline, const svslam_bm_params *p,
+                    double min_depth, int max_pts_per_job, float *out_xyz, int *out_pix, int16_t *out_disp)
+    { return svslam_dense_cloud_batch(ctx_, n, jobs, cam_l, ext_l, baseline, p, min_depth, max_pts_per_job, out_xyz, out_pix, out_disp); }
     int track(int n, svslam_track_job *jobs, const void *const *imgs, const int *strides, int is_device,
               int total, const double *cam, const float *prev_xy, float *next_xy, const uint8_t *has_mp,
               const double *xyz, uint8_t *status, uint8_t *outlier, const svslam_lk_params *p, double chi2_th)

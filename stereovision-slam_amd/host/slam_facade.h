@@ -13,6 +13,8 @@
 //   VisualOdometry  src/visual_odometry.cpp:24-224          initialize step run GetFrontendStatus
 //                                                           saveSLAMOutputInFile
 //   Map        include/StereoVisionSLAM/map.h               read-only views (keyframes, landmarks)
+//   DenseReconstruction  src/dense_reconstruction.cpp:13-238  Initialize DenseReconstruct  (the second program,
+//                                                           run_dense_reconstruction: keyframes.txt -> dense_map.pcd)
 //
 // Differences, all forced by the missing third-party libraries: cv::Mat becomes facade::Image (u8, one
 // channel), Sophus::SE3d becomes svs::SE3 (same 7 doubles), Frame::Ptr / Camera::Ptr stay shared_ptrs.
@@ -536,6 +538,187 @@ private:
     std::shared_ptr<FrontendT<K>> frontend_;
     std::shared_ptr<Backend> backend_;
     Map::Ptr map_;
+};
+
+// ---- DenseReconstruction (src/dense_reconstruction.cpp, include/StereoVisionSLAM/dense_reconstruction.h)
+// Reads the dense config (slam_output_dir = the keyframes.txt VisualOdometry::saveSLAMOutputInFile wrote, left_cam_index,
+// right_cam_index, output_dir), runs cv::StereoBM(128, 15) and the back-projection of every keyframe on the device
+// (svslam_dense_cloud_batch, several keyframes per call) and writes output_dir/dense_map.pcd.
+// Differences from the reference, all stated in DESIGN 9: the image reader is GREYSCALE (facade::imread), so r = g = b = the
+// grey value of the left pixel; PCL's StatisticalOutlierRemoval (k = 50) and the 2 cm VoxelGrid (:175-209) are not built, the
+// file holds the unfiltered merge of the keyframe clouds in keyframe order; the file goes to output_dir itself, not into a
+// time-stamped folder below it; as everywhere in this facade the 1/2 decimation of Dataset::FrameById happens on the device.
+struct DenseKeyframe { unsigned long image_id; SE3 T_cw; };
+
+// keyframes_poses_.push_back(Sophus::SE3f(T)) ... .cast<double>() (src/dense_reconstruction.cpp:59-72, :160): the twelve numbers
+// of a keyframes.txt record are FLOATS; SE3f's constructor turns the rotation block into a quaternion IN FLOAT (Eigen's
+// matrix-to-quaternion branches: trace > 0, else the largest diagonal entry), cast<double>() widens it and SO3d's
+// constructor normalises it in double; the translation is widened.  Plain + - * / sqrt on floats, then on doubles, so a
+// restatement in another language gives the same bits (only Eigen's summation order inside normalize() is not pinned).
+inline SE3 se3_from_float_rows(const float m[12])
+{
+    const float R[3][3] = { { m[0], m[1], m[2] }, { m[4], m[5], m[6] }, { m[8], m[9], m[10] } };
+    float q[4];                                    // x y z w
+    float t = R[0][0] + R[1][1] + R[2][2];
+    if (t > 0.f) {
+        t = std::sqrt(t + 1.0f);
+        q[3] = 0.5f * t;
+        t = 0.5f / t;
+        q[0] = (R[2][1] - R[1][2]) * t; q[1] = (R[0][2] - R[2][0]) * t; q[2] = (R[1][0] - R[0][1]) * t;
+    } else {
+        int i = 0;
+        if (R[1][1] > R[0][0]) i = 1;
+        if (R[2][2] > R[i][i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = std::sqrt(R[i][i] - R[j][j] - R[k][k] + 1.0f);
+        q[i] = 0.5f * t;
+        t = 0.5f / t;
+        q[3] = (R[k][j] - R[j][k]) * t; q[j] = (R[j][i] + R[i][j]) * t; q[k] = (R[k][i] + R[i][k]) * t;
+    }
+    const double qd[4] = { q[0], q[1], q[2], q[3] };
+    const double n = std::sqrt(qd[0] * qd[0] + qd[1] * qd[1] + qd[2] * qd[2] + qd[3] * qd[3]);
+    SE3 T;
+    for (int i = 0; i < 4; ++i) T.v[i] = qd[i] / n;
+    T.v[4] = m[3]; T.v[5] = m[7]; T.v[6] = m[11];
+    return T;
+}
+
+template <class K>
+class DenseReconstructionT {
+public:
+    explicit DenseReconstructionT(const std::string &config_file_path) : config_file_path_(config_file_path) {}
+
+    void Initialize()                             // :18-90
+    {
+        if (!config_.Load(config_file_path_)) throw SLAMException("Can not open the dense reconstruction config file.");
+        slam_output_dir_ = config_.Str("slam_output_dir");
+        left_cam_index_ = (int)config_.Num("left_cam_index", 0);
+        right_cam_index_ = (int)config_.Num("right_cam_index", 1);
+        std::ifstream slam_fp(slam_output_dir_);
+        if (!slam_fp) throw SLAMException("Can not open SLAM pipeline's output file.");
+        slam_fp >> data_sequence_path_;
+        slam_fp >> left_camera_index_in_slam_;
+        keyframes_.clear();
+        while (!slam_fp.eof()) {
+            unsigned long image_id;
+            slam_fp >> image_id;
+            if (slam_fp.fail()) break;
+            float m[12];
+            bool ok = true;
+            for (int i = 0; i < 12 && ok; ++i) { slam_fp >> m[i]; ok = !slam_fp.fail(); }        // parsed as float, like slam_fp >> T(i, j)
+            if (!ok) break;
+            keyframes_.push_back(DenseKeyframe{ image_id, se3_from_float_rows(m) });
+        }
+        dataset_.reset(new Dataset(data_sequence_path_, left_cam_index_, right_cam_index_));
+        if (!dataset_->initialize()) throw SLAMException("Cannot initialize object to read dataset.");
+        params_.num_disparities = num_disparities_; params_.block_size = blockSize_;
+        params_.pre_filter_cap = 31; params_.texture_threshold = 10; params_.uniqueness_ratio = 15; params_.reserved = 0;
+        xyz_.clear(); grey_.clear();
+    }
+
+    void DenseReconstruct()                       // :92-238
+    {
+        if (!dataset_) throw SLAMException("DenseReconstruction: Initialize() first");
+        const Camera::Ptr cl = dataset_->GetCamera(left_cam_index_), cr = dataset_->GetCamera(right_cam_index_);
+        // baseline = |pose_inv_.translation() of the two cameras| (:122-124); the kernel takes fx and it as floats (:120, :124)
+        const SE3 il = cl->pose.inverse(), ir = cr->pose.inverse();
+        const double baseline = std::sqrt((il.v[4] - ir.v[4]) * (il.v[4] - ir.v[4]) + (il.v[5] - ir.v[5]) * (il.v[5] - ir.v[5]) +
+                                          (il.v[6] - ir.v[6]) * (il.v[6] - ir.v[6]));
+        double cam[4];
+        cl->k4(cam);
+        const int B = 8;                           // keyframes per device call
+        xyz_.clear(); grey_.clear();
+        std::vector<float> xyz;
+        std::vector<int> pix;
+        for (size_t k0 = 0; k0 < keyframes_.size(); k0 += (size_t)B) {
+            const int nb = (int)std::min<size_t>((size_t)B, keyframes_.size() - k0);
+            std::vector<Frame::Ptr> frames;
+            for (int i = 0; i < nb; ++i) {
+                Frame::Ptr f = dataset_->FrameById(keyframes_[k0 + (size_t)i].image_id);
+                if (!f) throw SLAMException("DenseReconstruction: cannot read the images of keyframe " + std::to_string(keyframes_[k0 + (size_t)i].image_id));
+                if (!kernels_) create(f->left_img_.cols, f->left_img_.rows);
+                if (f->left_img_.cols != src_w_ || f->left_img_.rows != src_h_ || f->right_img_.cols != src_w_ || f->right_img_.rows != src_h_)
+                    throw SLAMException("frame size changed");
+                frames.push_back(f);
+            }
+            std::vector<int> slots; std::vector<const void *> imgs; std::vector<int> strides;
+            std::vector<svslam_dense_job> jobs((size_t)nb);
+            const int cap = w_ * h_;
+            for (int i = 0; i < nb; ++i) {
+                slots.push_back(2 * i); slots.push_back(2 * i + 1);
+                imgs.push_back(frames[(size_t)i]->left_img_.data.data()); imgs.push_back(frames[(size_t)i]->right_img_.data.data());
+                strides.push_back(src_w_); strides.push_back(src_w_);
+                svslam_dense_job &j = jobs[(size_t)i];
+                j.slot_left = 2 * i; j.slot_right = 2 * i + 1; j.pt_ofs = i * cap; j.n_points = 0;
+                std::memcpy(j.T_cw, keyframes_[k0 + (size_t)i].T_cw.v, sizeof(j.T_cw));
+            }
+            if (kernels_->pyramid_decimate(2 * nb, slots.data(), imgs.data(), strides.data(), src_w_, src_h_, 0) != 0)
+                throw SLAMException(std::string("DenseReconstruction: ") + kernels_->last_error());
+            xyz.resize(3 * (size_t)cap * (size_t)nb); pix.resize((size_t)cap * (size_t)nb);
+            if (kernels_->dense_cloud(nb, jobs.data(), cam, cl->pose.v, baseline, &params_, 1.0, cap, xyz.data(), pix.data(), nullptr) != 0)
+                throw SLAMException(std::string("DenseReconstruction: ") + kernels_->last_error());
+            for (int i = 0; i < nb; ++i) {
+                const svslam_dense_job &j = jobs[(size_t)i];
+                const Image &src = frames[(size_t)i]->left_img_;
+                xyz_.insert(xyz_.end(), xyz.begin() + 3 * (long)j.pt_ofs, xyz.begin() + 3 * ((long)j.pt_ofs + j.n_points));
+                for (int p = 0; p < j.n_points; ++p) {
+                    const int y = pix[(size_t)j.pt_ofs + (size_t)p] / w_, x = pix[(size_t)j.pt_ofs + (size_t)p] - y * w_;
+                    grey_.push_back(src.data[(size_t)(2 * y) * (size_t)src_w_ + (size_t)(2 * x)]);     // dst(x, y) = src(2x, 2y) (src/dataset.cpp:162-165)
+                }
+            }
+        }
+        const std::string output_dir = config_.Str("output_dir", ".");
+        map_file_ = output_dir + "/dense_map.pcd";
+        if (!SavePCDFileBinary(map_file_)) throw SLAMException("DenseReconstruction: cannot write " + map_file_);
+    }
+
+    // pcl::io::savePCDFileBinary of a PointXYZRGB cloud: PCD v0.7, x y z rgb, the colour packed r << 16 | g << 8 | b into the
+    // 4 bytes of the rgb field
+    bool SavePCDFileBinary(const std::string &path) const
+    {
+        std::ofstream o(path, std::ios::binary);
+        if (!o) return false;
+        const size_t n = grey_.size();
+        o << "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\nTYPE F F F F\nCOUNT 1 1 1 1\nWIDTH " << n
+          << "\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS " << n << "\nDATA binary\n";
+        std::vector<char> rec(16 * n);
+        for (size_t i = 0; i < n; ++i) {
+            const uint32_t g = grey_[i], rgb = (g << 16) | (g << 8) | g;
+            std::memcpy(&rec[16 * i], &xyz_[3 * i], 12);
+            std::memcpy(&rec[16 * i + 12], &rgb, 4);
+        }
+        o.write(rec.data(), (std::streamsize)rec.size());
+        return (bool)o;
+    }
+
+    const std::vector<DenseKeyframe> &Keyframes() const { return keyframes_; }
+    size_t NumPoints() const { return grey_.size(); }
+    const std::string &MapFile() const { return map_file_; }
+    Dataset::Ptr dataset() { return dataset_; }
+    K *kernels() { return kernels_.get(); }
+
+private:
+    void create(int w, int h)
+    {
+        src_w_ = w; src_h_ = h;
+        w_ = (int)std::nearbyint(w * 0.5); h_ = (int)std::nearbyint(h * 0.5);
+        svslam_limits lim;
+        std::memset(&lim, 0, sizeof(lim));
+        lim.device = (int)config_.Num("device", 0); lim.width = w_; lim.height = h_; lim.max_slots = 16; lim.max_jobs = 16;     // 8 keyframes per call: 16 images in one pyramid call
+        lim.max_pts = 8; lim.max_corners = 8;
+        kernels_.reset(new K(lim));
+    }
+    std::string config_file_path_, slam_output_dir_, data_sequence_path_, map_file_;
+    ConfigFile config_;
+    int left_cam_index_ = 0, right_cam_index_ = 1, left_camera_index_in_slam_ = 0;
+    int num_disparities_ = 128, blockSize_ = 15;   // include/StereoVisionSLAM/dense_reconstruction.h:56-57
+    svslam_bm_params params_;
+    std::vector<DenseKeyframe> keyframes_;
+    Dataset::Ptr dataset_;
+    std::unique_ptr<K> kernels_;
+    int src_w_ = 0, src_h_ = 0, w_ = 0, h_ = 0;
+    std::vector<float> xyz_;                      // the merged cloud: x y z per point ...
+    std::vector<uint8_t> grey_;                   // ... and its grey value
 };
 
 } // namespace facade

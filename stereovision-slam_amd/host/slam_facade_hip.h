@@ -8,5 +8,6 @@ namespace svs {
 namespace facade {
 using Frontend = FrontendT<HipKernels>;
 using VisualOdometry = VisualOdometryT<HipKernels>;
+using DenseReconstruction = DenseReconstructionT<HipKernels>;
 } // namespace facade
 } // namespace svs
