@@ -176,7 +176,7 @@ typedef struct svslam_bm_params {
     int block_size;        /* 15  */
     int pre_filter_cap;    /* 31  */
     int texture_threshold; /* 10  */
-    int uniqueness_ratio;  /* 15  */
+    int uniqueness_ratio;  /* 15; 0 disables the uniqueness test (OpenCV: if( uniquenessRatio > 0 )), 1..10000 apply it */
     int reserved;
 } svslam_bm_params;
 typedef struct svslam_bm_job { int slot_left, slot_right; } svslam_bm_job;   /* level 0 of each pyramid slot */

@@ -180,7 +180,9 @@ __global__ __launch_bounds__(BM_THREADS) void k_stereo_bm(const BmJob *jobs, con
             if (v <= minsad) { minsad = v; mind = part[(4 + q) * BM_TW + xi]; }
         }
         {
-            const int thr = minsad + minsad * P.uniq / 100;
+            // uniquenessRatio 0 switches the test off (stereobm.cpp: if( uniquenessRatio > 0 )): no SAD is <= -1.  The scan itself stays
+            // as it is for every ratio
+            const int thr = P.uniq > 0 ? minsad + minsad * P.uniq / 100 : -1;
             bool fail = false;
             for (int d = dlo; d < dlo + dq; d += 2) {
                 const unsigned int u = sadw[(size_t)(d >> 1) * BM_TW + xi];

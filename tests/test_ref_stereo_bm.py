@@ -151,3 +151,180 @@ def test_cloud_order_and_gate():
     assert pix.tolist() == [3 * 5 + 1, 0 * 5 + 3, 1 * 5 + 3]    # x outer, y inner
     z = np.float32(np.float32(cam[0]) * np.float32(0.537166)) / np.float32(20.0)
     assert xyz[0, 2] == z and xyz.dtype == np.float32
+
+
+# ---- inputs built for a purpose, shared with the GPU sweep (tests/test_gpu_stereo_bm.py) ------------------------------------
+def band_pair(w, h, nd, seed=21):
+    """four horizontal bands of random texture with exact integer shifts, one per quarter of [0, nd): 2 (next to the
+    SAD(-1) := SAD(1) end), the last disparity of quarter 1, the first of quarter 2, and nd - 1 (the SAD(nd) := SAD(nd - 2) end)"""
+    rng = np.random.default_rng(seed)
+    dq = nd // 4
+    wide = rng.integers(0, 256, (h, w + nd), dtype=np.uint8)
+    left, right = wide[:, :w].copy(), np.empty((h, w), np.uint8)
+    edges = [round(k * h / 4) for k in range(5)]
+    for k, s in enumerate((2, 2 * dq - 1, 2 * dq, nd - 1)):
+        right[edges[k]:edges[k + 1]] = wide[edges[k]:edges[k + 1], s:s + w]       # right[x - s] = left[x]
+    return left, right
+
+
+def texture_ramp_pair(w, h, nd, shift=7, seed=31):
+    """texture that grows with the column, for texture_threshold: over the computed region (x from nd on) a flat tenth (texture sum 0),
+    then grey 100 with isolated +-1 dots whose density rises to 2 % (one dot alone in a window has the texture sum 2+2+4x1 = 8, an
+    exact match and no second one: valid unless the texture test drops it), then noise whose amplitude doubles every 9 % of the
+    width.  right = left shifted by `shift`."""
+    rng = np.random.default_rng(seed)
+    x = (np.arange(w + shift, dtype=np.float64) - nd) / (w - nd)
+    u = rng.random((h, w + shift)); noise = rng.uniform(-1.0, 1.0, (h, w + shift))
+    dots = np.sign(noise) * (u < np.clip((x - 0.10) / 0.35, 0, 1)[None] * 0.02)
+    amp = np.where(x < 0.45, 0.0, 0.8 * np.exp(8.0 * (x - 0.45)))
+    wide = np.clip(np.rint(100.0 + np.where(x[None] < 0.45, dots, amp[None] * noise)), 0, 255).astype(np.uint8)
+    return wide[:, :w].copy(), wide[:, shift:].copy()
+
+
+def uniqueness_ramp_pair(w, h, nd, shift=7, period=11, seed=41):
+    """a second, weaker match that fades with the column, for uniqueness_ratio: over the computed region a flat tenth, then
+    alpha P + (1 - alpha) N with P of period 11 along the row (a second match at shift + 11 and shift - 11... as good as the noise
+    in the right image lets it be) and N random, alpha falling from 1 to 0 as a cube, the right image shifted and with +-6 grey
+    levels of noise; the last 12 % are N alone without noise: min SAD = 0 there, unique at any ratio"""
+    rng = np.random.default_rng(seed)
+    n = w + shift
+    x = (np.arange(n, dtype=np.float64) - nd) / (w - nd)
+    P = np.tile(rng.uniform(-1, 1, (h, period)), (1, n // period + 1))[:, :n]
+    N = rng.uniform(-1, 1, (h, n))
+    alpha = 1.0 - np.clip((x - 0.10) / 0.78, 0.0, 1.0) ** 3
+    wide = 128.0 + np.where(x < 0.10, 0.0, 60.0)[None] * (alpha[None] * P + (1 - alpha[None]) * N)
+    left = np.clip(np.rint(wide[:, :w]), 0, 255).astype(np.uint8)
+    eps = rng.uniform(-6.0, 6.0, (h, w)) * (x[shift:] < 0.88)[None]
+    right = np.clip(np.rint(wide[:, shift:] + eps), 0, 255).astype(np.uint8)
+    return left, right
+
+
+def tie_pair(w, h, nd, shift=5, seed=51):
+    """exact SAD ties between disparities of different quarters of [0, nd).  Upper half: every row has the period nd / 2 (rows
+    differ), so SAD(d) = SAD(d + nd / 2): the minimum is tied between quarters 0 and 2 or 1 and 3.  Lower half: a constant
+    gradient of 2 grey levels per column (w <= 128), whose prefiltered image is constant: every SAD is 0, all nd disparities tie."""
+    rng = np.random.default_rng(seed)
+    assert w <= 128 and nd % 4 == 0
+    p = nd // 2
+    top = np.tile(rng.integers(0, 256, (h, p), dtype=np.uint8), (1, (w + shift) // p + 1))[:, :w + shift]
+    left, right = top[:, :w].copy(), top[:, shift:].copy()
+    left[h // 2:] = right[h // 2:] = (2 * np.arange(w)).astype(np.uint8)[None]
+    return left, right
+
+
+def bw_pair(w, h, shift=7, seed=11):
+    """2 x 2 blocks of 0 / 255: the prefilter saturates at both ends of [0, 2 cap]"""
+    rng = np.random.default_rng(seed)
+    wide = (rng.random((h // 2 + 1, (w + shift) // 2 + 1)) < 0.5).astype(np.uint8) * 255
+    wide = np.repeat(np.repeat(wide, 2, 0), 2, 1)[:h, :w + shift]
+    return np.ascontiguousarray(wide[:, :w]), np.ascontiguousarray(wide[:, shift:])
+
+
+def region_of(disp, nd, bs):
+    r, (h, w) = bs // 2, disp.shape
+    return disp[r:h - r, nd - 1 + r:w - r]
+
+
+# ---- the brute-force twin ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("h", [9, 8, 1])
+def test_bruteforce_prefilter_equals_the_vectorised_one(h):
+    rng = np.random.default_rng(60 + h)
+    img = rng.integers(100, 116, (h, 23), dtype=np.uint8)                       # gradients of both signs, within and beyond every cap
+    sat = np.tile(np.array([0, 0, 255, 255], np.uint8), (h, 6))[:, :23]
+    for cap in (1, 31, 63):
+        for im in (img, sat, img[:, :3], img[:, :2]):
+            assert np.array_equal(rbm.prefilter_xsobel_bruteforce(im, cap), rbm.prefilter_xsobel(im, cap)), (h, cap, im.shape)
+    if h > 1:
+        assert len(np.unique(rbm.prefilter_xsobel(img, 31)[:h - (h & 1)])) > 31          # (more than half of [0, 62] occurs: not two constant images)
+
+
+def _grid_input(svs, name, w, h, nd):
+    if name == "synthetic":
+        left, right = svs.synth_pair(1, 0, w=620, h=188)
+        # a window of the pair where the scene's disparity is below 16: the far end of the tunnel, around the principal point
+        y0, x0 = 92 - h // 2, 303 - w // 2
+        return left[y0:y0 + h, x0:x0 + w].copy(), right[y0:y0 + h, x0:x0 + w].copy()
+    if name == "black_white":
+        return bw_pair(w, h)
+    if name == "period8":
+        per = hand_pairs()["period8"][0]
+        return per[:h, :w].copy(), per[:h, 3:3 + w].copy()                               # shifted by 3: ties at 3, 11, 19, ..
+    return tie_pair(w, h, nd)
+
+
+@pytest.mark.parametrize("bs", [5, 7, 13])
+@pytest.mark.parametrize("nd", [16, 48])
+@pytest.mark.parametrize("name", ["synthetic", "black_white", "period8", "ties"])
+def test_bruteforce_equals_the_restatement_bit_for_bit(svs, name, nd, bs):
+    """The whole grid cap {1, 31, 63} x texture_threshold {0, 10, the region's median texture sum} x uniqueness_ratio {0, 1, 15, 100}
+    on images of 12 (nd 16) or 8 (nd 48) computed columns and 7 or 8 computed rows (at most 67 x 20)."""
+    r = bs // 2
+    w, h = nd - 1 + 2 * r + (12 if nd == 16 else 8), 2 * r + 7 + (bs == 7)               # bs 7: an even height (14)
+    left, right = _grid_input(svs, name, w, h, nd)
+    seen, valid, maps = set(), [], {}
+    for cap in (1, 31, 63):
+        _, tex = rbm.sad_volume(left, right, nd, bs, cap)
+        for thr in (0, 10, int(np.median(tex))):
+            for uniq in (0, 1, 15, 100):
+                prm = dict(num_disparities=nd, block_size=bs, pre_filter_cap=cap, texture_threshold=thr, uniqueness_ratio=uniq)
+                ref = rbm.stereo_bm(left, right, **prm)
+                got = rbm.stereo_bm_bruteforce(left, right, **prm)
+                assert got.dtype == np.int16 and np.array_equal(got, ref), (prm, np.argwhere(got != ref)[:4])
+                seen.add(ref.tobytes()); valid.append((region_of(ref, nd, bs) > 0).mean())
+                maps[(cap, thr if thr in (0, 10) else "median", uniq)] = ref.tobytes()
+    # which parameters decide anything here: two parameter sets that differ in that parameter alone give different maps
+    axes = {name_: any(a != b for ka, a in maps.items() for kb, b in maps.items()
+                       if ka[i] != kb[i] and all(ka[j] == kb[j] for j in range(3) if j != i))
+            for i, name_ in enumerate(("cap", "tex", "uniq"))}
+    print("%s nd %d bs %d (%dx%d): %d distinct maps of 36, valid share %.2f .. %.2f, deciding: %s" %
+          (name, nd, bs, w, h, len(seen), min(valid), max(valid), [k for k, v in axes.items() if v]))
+    assert max(valid) > 0.5                                     # something is matched
+    # natural texture: all three parameters decide pixels.  Exact ties: the uniqueness test decides (ratio 0 against the rest) and,
+    # in the constant-gradient half, the cap byte of the texture sum.  0 / 255 blocks saturate at every cap and match exactly
+    # (minimum 0): only the median texture threshold cuts.  Period 8 is all-or-nothing on the ratio
+    want = {"synthetic": {"cap", "tex", "uniq"}, "ties": {"uniq"}, "black_white": {"tex"}, "period8": {"uniq"}}[name]
+    assert all(axes[k] for k in want), axes
+
+
+def test_period8_at_ratio_0_keeps_the_largest_tied_disparity():
+    """left = right with period 8: SAD(d) = SAD(d + 8) exactly, the minimum 0 at d = 0, 8, 16, 24.  OpenCV skips the uniqueness
+    scan at uniquenessRatio 0 and its strict `<` over descending d keeps the largest: arg-min 24 = the largest d < nd = 32 that is
+    congruent to the shift (0) modulo 8, at EVERY pixel; at ratio 1 every pixel is filtered.
+
+    The arg-min is not `value >> 4`: value = (256 d + t + 15) >> 4 with the sub-pixel term t = 128 (p - n) / max(p, n), |t| <= 128,
+    and p - n = SAD(23) - SAD(25) is the difference of the window's two boundary columns, not 0 (the window is 9 wide, the period
+    8).  Here t is in [-31, 47]: the values are 383, 384 and 386, and 383 >> 4 = 23.  The integer disparity of a value is therefore
+    taken as (value + 8) >> 4 (nearest, exact for |t| < 113), and the value is additionally held to 16 x 24 +- 8 (half a pixel),
+    which is what |t| <= 128 allows and no more; and to the value worked out by hand from the window sums SAD(23) and SAD(25)."""
+    left, right, prm, _ = hand_pairs()["period8"]
+    nd, bs = prm["num_disparities"], prm["block_size"]
+    shift = 0
+    region = region_of(rbm.stereo_bm(left, right, uniqueness_ratio=0, **prm), nd, bs).astype(np.int32)
+    print("period8, ratio 0: values", dict(zip(*np.unique(region, return_counts=True))))
+    check_period8_ratio0(region, nd, shift, rbm.sad_volume(left, right, nd, bs)[0])
+    assert (region_of(rbm.stereo_bm(left, right, uniqueness_ratio=1, **prm), nd, bs) == -16).all()
+    sad, _ = rbm.sad_volume(left, right, nd, bs)
+    assert (sad[0] == 0).all() and all(np.array_equal(sad[d], sad[d + 8]) for d in range(nd - 8))
+
+
+def check_period8_ratio0(region, nd, shift, sad):
+    d = (region + 8) >> 4
+    assert region.size > 0 and (region > 0).all()                                        # every pixel of the region is valid
+    assert (d % 8 == shift % 8).all() and (d >= nd - 8).all()
+    assert (np.abs(region - 16 * d) <= 8).all()
+    # the value by hand: arg-min D = the largest d < nd congruent to the shift, SAD(D) = 0, p = SAD(D - 1), n = SAD(D + 1) straight from
+    # the window sums — nothing of the matcher's arg-min, uniqueness or sub-pixel code
+    D = nd - 8 + shift % 8
+    p, n = sad[D - 1], sad[D + 1]
+    assert (sad[D] == 0).all() and (p > 0).all() and (n > 0).all()
+    num, den = (p - n) * 256, p + n + np.abs(p - n)
+    t = np.sign(num) * (np.abs(num) // den)                                              # C division
+    assert np.array_equal(region, (D * 256 + t + 15) >> 4)
+
+
+def test_ratio_0_only_adds_pixels_and_ratio_1_is_a_test():
+    """on the uniqueness ramp: the map at ratio 0 equals the map at ratio 1 wherever that one is valid, and has more valid pixels"""
+    left, right = uniqueness_ramp_pair(160, 31, 32)
+    a = rbm.stereo_bm(left, right, num_disparities=32, block_size=9, uniqueness_ratio=0)
+    b = rbm.stereo_bm(left, right, num_disparities=32, block_size=9, uniqueness_ratio=1)
+    assert np.array_equal(a[b != -16], b[b != -16]) and (a != -16).sum() > (b != -16).sum() > 0
