@@ -197,7 +197,8 @@ int svslam_stereo_bm_strip_rows(svslam_ctx *ctx, int njobs, const svslam_bm_para
  * x outer, y inner; out_pix holds y * width + x of each point, for the caller to colour it from the
  * image it holds.  n_points (out) beyond max_pts_per_job is an error, nothing of that call is returned.
  * out_disp_or_null: the disparity maps as svslam_stereo_bm_batch returns them.
- * Not built: StatisticalOutlierRemoval and the VoxelGrid of :175-209 (PCL).                        */
+ * The StatisticalOutlierRemoval and the VoxelGrid of :175-209 (PCL) are calls of their own, below:
+ * svslam_cloud_sor_batch and svslam_cloud_voxel_grid take the clouds this call returned.             */
 typedef struct svslam_dense_job {
     int    slot_left, slot_right;
     int    pt_ofs;         /* in: where this job's points start in out_xyz / out_pix */
@@ -209,6 +210,27 @@ int svslam_dense_cloud_batch(svslam_ctx *ctx, int njobs, svslam_dense_job *jobs,
                              const double ext_l[7], double baseline, const svslam_bm_params *p,
                              double min_depth, int max_pts_per_job, float *out_xyz, int *out_pix,
                              int16_t *out_disp_or_null);
+
+/* ---- the cloud filters of run_dense_reconstruction -----------------------------------------
+ * The numeric contract of both is tests/ref_cloud_filters.py (parity with PCL itself is unpinned).
+ * pcl::StatisticalOutlierRemoval (src/dense_reconstruction.cpp:180-184, :195-199) on nseg independent clouds:
+ * segment s is xyz[3*seg_ofs[s]] .. xyz[3*seg_ofs[s+1]].  out_keep: 1 / 0 per point; out_mean_dist_or_null;
+ * out_threshold[nseg] (NaN where the segment has fewer than mean_k + 1 points: all kept).  mean_k 1 .. 64.
+ * out_keep and out_mean_dist_or_null are indexed like the points (point seg_ofs[s] + i at [seg_ofs[s] + i]).
+ * The exact k-nearest-neighbour mean distances come from the device; the statistics, the threshold and the
+ * mask are computed on the host in PCL's sequential order.  A non-finite coordinate is an error (PCL's
+ * branch for such points is not built); at most 2^30 points per call.                                   */
+int svslam_cloud_sor_batch(svslam_ctx *ctx, int nseg, const int64_t *seg_ofs, const float *xyz, int mean_k,
+                           double stddev_mul, uint8_t *out_keep, float *out_mean_dist_or_null, double *out_threshold);
+/* pcl::VoxelGrid (:203-209), downsample_all_data: returns the number of output points in *out_n (<= n), out_overflowed = 1
+ * and output = input where PCL's int32 index guard trips ("Leaf size is too small for the input dataset").
+ * rgb: 3 bytes per point.  out_xyz / out_rgb hold n points.  One output point per occupied voxel, in ascending
+ * voxel index; a voxel's sums run in ascending point index.                                              */
+int svslam_cloud_voxel_grid(svslam_ctx *ctx, int64_t n, const float *xyz, const uint8_t *rgb, double leaf,
+                            float *out_xyz, uint8_t *out_rgb, int64_t *out_n, int *out_overflowed);
+/* measurement hook: since the last call of it, the nearest-neighbour queries svslam_cloud_sor_batch ran and how many
+ * of them had to scan a larger block of cells than the one they started with */
+int svslam_debug_cloud_sor_climbs(svslam_ctx *ctx, long long *out_queries, long long *out_climbed);
 
 /* ---- stereo triangulation ----------------------------------------------
  * Replaces slam::triangulation() (include/StereoVisionSLAM/algorithm.h:10-87)
@@ -485,7 +507,8 @@ int svslam_sync(svslam_ctx *ctx);
 /* ---- kernel timing (HIP events on the context's stream) -------------------
  * Accumulated per kernel family since the last reset; used by bench.py for
  * the roofline entry.  family: 0 pyramid, 1 lk, 2 gftt, 3 triangulate,
- * 4 pose_only, 5 local_ba, 6 stereo_bm (units = jobs).
+ * 4 pose_only, 5 local_ba, 6 stereo_bm (units = jobs), 12 cloud_filter (units = points; appended
+ * after the last number in use, nothing moved).
  * Development families follow and are NOT stable numbers: with stereo_bm taking 6, the
  * per-kernel split moved from 6-9 to 7-10 and the local-BA solver interval from 10 to 11.
  * A caller that passed those raw numbers must move with them (Python addresses them by name). */

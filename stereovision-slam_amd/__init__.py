@@ -19,7 +19,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 ABI_SYMBOLS = [
     "svslam_create", "svslam_destroy", "svslam_last_error", "svslam_build_info",
     "svslam_pyramid_batch", "svslam_pyramid_decimate_batch", "svslam_set_source_size", "svslam_set_low_latency", "svslam_set_pose_only_xtol", "svslam_get_pose_only_xtol", "svslam_pyramid_read",
-    "svslam_pyramid_read_padded", "svslam_stereo_bm_batch", "svslam_stereo_bm_strip_rows", "svslam_dense_cloud_batch", "svslam_lk_batch", "svslam_gftt_batch", "svslam_gftt_eigmap", "svslam_triangulate_batch",
+    "svslam_pyramid_read_padded", "svslam_stereo_bm_batch", "svslam_stereo_bm_strip_rows", "svslam_dense_cloud_batch", "svslam_cloud_sor_batch", "svslam_cloud_voxel_grid", "svslam_debug_cloud_sor_climbs", "svslam_lk_batch", "svslam_gftt_batch", "svslam_gftt_eigmap", "svslam_triangulate_batch",
     "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect",
     "svslam_track_batch", "svslam_rtrack_batch", "svslam_rtrack_upload",
     "svslam_sba_io_doubles", "svslam_sba_open", "svslam_sba_phase", "svslam_sba_close",
@@ -35,10 +35,12 @@ DEBUG_FAMILIES = {"dbg0": 7, "dbg1": 8, "dbg2": 9, "dbg3": 10}     # per-kernel 
 # intervals nested inside a family: the local-BA solver kernel alone (k_local_ba_t<0, 1, EID>, or the low-latency solver's kernels)
 # inside "local_ba" (= map gather + structure build + solver + scatter)
 KERNEL_FAMILIES = {"ba_solve": 11}
+CLOUD_FAMILIES = {"cloud_filter": 12}      # the outlier removal and the voxel grid of the dense program (units = points); appended, nothing renumbered
 # the HIP kernel(s) behind each timing family at the batch operating point (what a rocprofv3 --kernel-trace --stats row is named)
 FAMILY_KERNELS = {"pyramid": ["k_pyr_fused"], "lk": ["k_lk"], "gftt": ["k_gftt_eig3", "k_gftt_select2"], "triangulate": ["k_triangulate"],
                   "pose_only": ["k_pose_only"], "local_ba": ["k_dmap_ba_gather", "k_ba_build", "k_local_ba_t", "k_dmap_ba_scatter"],
-                  "ba_solve": ["k_local_ba_t"], "stereo_bm": ["k_bm_fill", "k_stereo_bm", "k_dense_cloud"]}
+                  "ba_solve": ["k_local_ba_t"], "stereo_bm": ["k_bm_fill", "k_stereo_bm", "k_dense_cloud"],
+                  "cloud_filter": ["k_cf_keys", "k_cf_gather", "k_cf_knn", "k_vg_keys", "k_vg_heads", "k_vg_starts", "k_vg_reduce"]}
 
 
 class Limits(C.Structure):
@@ -128,6 +130,9 @@ def load():
         L.svslam_set_pose_only_xtol.argtypes = [C.c_void_p, C.c_double]
         L.svslam_get_pose_only_xtol.argtypes = [C.c_void_p]
         L.svslam_get_pose_only_xtol.restype = C.c_double
+        L.svslam_cloud_sor_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.svslam_cloud_voxel_grid.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_int64), C.POINTER(C.c_int)]
         L.svslam_dev_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         L.svslam_dev_free.argtypes = [C.c_void_p, C.c_void_p]
         L.svslam_dev_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -264,7 +269,7 @@ class Context:
 
     def timing_get(self, family):
         ms, n, u = C.c_double(), C.c_longlong(), C.c_longlong()
-        fam = next(t[family] for t in (FAMILIES, KERNEL_FAMILIES, DENSE_FAMILIES, DEBUG_FAMILIES) if family in t)
+        fam = next(t[family] for t in (FAMILIES, KERNEL_FAMILIES, DENSE_FAMILIES, CLOUD_FAMILIES, DEBUG_FAMILIES) if family in t)
         self._chk(self.L.svslam_timing_get(self.h, fam, C.byref(ms), C.byref(n), C.byref(u)), "timing")
         return ms.value, n.value, u.value
 
@@ -356,6 +361,39 @@ class Context:
                                                   C.c_double(min_depth), cap, _p(xyz), _p(pix), _p(disp)), "dense_cloud_batch")
         return [(xyz[j.pt_ofs:j.pt_ofs + j.n_points].copy(), pix[j.pt_ofs:j.pt_ofs + j.n_points].copy(), disp[i].copy())
                 for i, j in enumerate(arr[:n])]
+
+    # ---- cloud filters ---------------------------------------------------
+    def cloud_sor(self, clouds, mean_k=50, stddev_mul=1.0):
+        """pcl::StatisticalOutlierRemoval on a list of [n, 3] float32 clouds, one batched call (svslam_cloud_sor_batch).
+        returns per cloud (keep bool [n], mean_dist float32 [n], threshold float; NaN and all kept below mean_k + 1 points)"""
+        cl = [_f32(x, 3) for x in clouds]
+        ofs = np.zeros(len(cl) + 1, np.int64)
+        ofs[1:] = np.cumsum([len(x) for x in cl])
+        n = int(ofs[-1])
+        xyz = np.ascontiguousarray(np.concatenate(cl)) if n else np.zeros((1, 3), np.float32)
+        keep = np.zeros(max(n, 1), np.uint8); md = np.zeros(max(n, 1), np.float32); thr = np.zeros(max(len(cl), 1))
+        self._chk(self.L.svslam_cloud_sor_batch(self.h, len(cl), _p(ofs), _p(xyz), int(mean_k), C.c_double(stddev_mul), _p(keep), _p(md),
+                                                _p(thr)), "cloud_sor_batch")
+        return [(keep[a:b].astype(bool), md[a:b].copy(), float(thr[i])) for i, (a, b) in enumerate(zip(ofs[:-1], ofs[1:]))]
+
+    def cloud_sor_climbs(self):
+        """measurement hook (svslam_debug_cloud_sor_climbs): (queries, queries that scanned more than their first block) since the last call"""
+        q, k = C.c_longlong(), C.c_longlong()
+        self._chk(self.L.svslam_debug_cloud_sor_climbs(self.h, C.byref(q), C.byref(k)), "debug_cloud_sor_climbs")
+        return q.value, k.value
+
+    def cloud_voxel_grid(self, xyz, rgb, leaf=0.02):
+        """pcl::VoxelGrid (svslam_cloud_voxel_grid): xyz float32 [n, 3], rgb uint8 [n, 3] -> (xyz, rgb, overflowed); overflowed:
+        PCL's int32 index guard tripped, the output is the input"""
+        xyz = _f32(xyz, 3); rgb = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+        n = len(xyz)
+        if len(rgb) != n:
+            raise ValueError("xyz and rgb differ in length")
+        oxyz = np.zeros((max(n, 1), 3), np.float32); orgb = np.zeros((max(n, 1), 3), np.uint8)
+        m, over = C.c_int64(0), C.c_int(0)
+        self._chk(self.L.svslam_cloud_voxel_grid(self.h, n, _p(xyz), _p(rgb), C.c_double(leaf), _p(oxyz), _p(orgb), C.byref(m), C.byref(over)),
+                  "cloud_voxel_grid")
+        return oxyz[:m.value].copy(), orgb[:m.value].copy(), bool(over.value)
 
     # ---- LK --------------------------------------------------------------
     def lk(self, jobs, params=None):

@@ -17,6 +17,7 @@
 #include <string>
 #include <tuple>
 #include <vector>
+#include <rocprim/rocprim.hpp>     // header-only: the two radix sorts and the scan of the cloud filters (k_cloud_filter.h)
 
 #include <dlfcn.h>
 // RCCL is bound with dlopen when a shared-map communicator is asked for; the few types and constants of its C API used here
@@ -43,6 +44,7 @@ typedef enum { ncclDouble = 8 } ncclDataType_t;
 #include "k_ba_ll.h"
 #include "k_dmap.h"
 #include "k_stereo_bm.h"
+#include "k_cloud_filter.h"
 
 #define SVSLAM_DMAP_CHUNK 512     /* keyframe jobs per svslam_dmap_keyframe_batch call the staging arena is sized for */
 #define SVSLAM_DMAP_EVICT_PER_JOB 512   /* evicted-landmark records per job of a call (shared by the call's jobs; the surplus waits) */
@@ -54,6 +56,7 @@ enum { FAM_PYR = 0, FAM_LK, FAM_GFTT, FAM_TRI, FAM_POSE, FAM_BA,
        FAM_BM,         // family 6 of svslam_timing_get: the dense-stereo kernels (k_bm_fill + k_stereo_bm [+ k_dense_cloud])
        FAM_DBG0, FAM_DBG1, FAM_DBG2, FAM_DBG3,      // development (SVSLAM_TIMING_SPLIT): 7 .. 10
        FAM_BA_SOLVE,   // 11: the local-BA solver kernel(s) alone, nested inside FAM_BA (gather + build + solve + scatter)
+       FAM_CF,         // 12: "cloud_filter", the outlier-removal and voxel-grid kernels with their sorts (units = points); appended, nothing moved
        FAM_COUNT };
 
 struct Timing {
@@ -97,6 +100,10 @@ struct svslam_ctx {
     GfttWork gw;
     // dense stereo scratch (svslam_stereo_bm_batch / svslam_dense_cloud_batch), allocated at first use for max_jobs images
     struct { int16_t *disp = nullptr; float *xyz = nullptr; int *pix = nullptr; } bm;
+    // cloud filters (svslam_cloud_sor_batch / svslam_cloud_voxel_grid): device buffers sized at first use, grown on demand
+    struct CfBuf { void *p = nullptr; size_t cap = 0; };
+    struct { CfBuf xyz, rgb, segs, keys, keys2, vals, vals2, soa, out, flag, pos, start, oxyz, orgb, tmp; unsigned *climbs = nullptr;
+             long long queries = 0, climbed = 0; } cf;
     // BA scratch
     BaWork bw;
     int bw_jobs = 0;          // problems per call the BA scratch holds
@@ -761,6 +768,9 @@ void svslam_destroy(svslam_ctx *c)
     }
     (void)hipFree(c->gw.keys); (void)hipFree(c->gw.counters);
     (void)hipFree(c->bm.disp); (void)hipFree(c->bm.xyz); (void)hipFree(c->bm.pix);
+    for (svslam_ctx::CfBuf *b : { &c->cf.xyz, &c->cf.rgb, &c->cf.segs, &c->cf.keys, &c->cf.keys2, &c->cf.vals, &c->cf.vals2, &c->cf.soa, &c->cf.out,
+                                  &c->cf.flag, &c->cf.pos, &c->cf.start, &c->cf.oxyz, &c->cf.orgb, &c->cf.tmp }) (void)hipFree(b->p);
+    (void)hipFree(c->cf.climbs);
     ba_work_free(c->bw);
     ll_release(c);
     if (c->d_ba_prof) (void)hipFree(c->d_ba_prof);
@@ -1243,6 +1253,202 @@ int svslam_dense_cloud_batch(svslam_ctx *c, int njobs, svslam_dense_job *jobs, c
         HIPCHK(c, hipMemcpy(out_pix + (size_t)jobs[i].pt_ofs, c->bm.pix + (size_t)i * cap, sizeof(int) * n, hipMemcpyDeviceToHost));
     }
     if (out_disp_or_null) HIPCHK(c, hipMemcpy(out_disp_or_null, c->bm.disp, sizeof(int16_t) * N * njobs, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ------------------------------------------------------------------ cloud filters (src/dense_reconstruction.cpp:175-209)
+// a device buffer of at least `bytes`; grown (with a quarter of headroom) when a call needs more than the last one
+static int cf_reserve(svslam_ctx *c, svslam_ctx::CfBuf &b, size_t bytes)
+{
+    if (bytes <= b.cap) return 0;
+    (void)hipFree(b.p);
+    b.p = nullptr; b.cap = 0;
+    const size_t want = bytes + bytes / 4 + 256;
+    if (hipMalloc(&b.p, want) != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        return fail(c, "cloud_filter: cannot allocate %zu bytes of device memory", want);
+    }
+    b.cap = want;
+    return 0;
+}
+static inline dim3 cf_grid(long long n) { return dim3((unsigned)((n + CF_THREADS - 1) / CF_THREADS)); }
+
+int svslam_cloud_sor_batch(svslam_ctx *c, int nseg, const int64_t *seg_ofs, const float *xyz, int mean_k, double stddev_mul, uint8_t *out_keep,
+                           float *out_mean_dist_or_null, double *out_threshold)
+{
+    if (!c) return -1;
+    if (mean_k < 1 || mean_k > CF_KMAX) return fail(c, "cloud_filter: mean_k %d out of [1, %d]", mean_k, CF_KMAX);
+    if (nseg < 0) return fail(c, "cloud_filter: %d segments", nseg);
+    if (nseg == 0) return 0;
+    if (!seg_ofs || !out_threshold) return fail(c, "cloud_filter: null seg_ofs / out_threshold");
+    for (int s = 0; s < nseg; ++s) if (seg_ofs[s + 1] < seg_ofs[s] || seg_ofs[s] < 0) return fail(c, "cloud_filter: seg_ofs must be non-negative and ascending (segment %d)", s);
+    const int64_t first = seg_ofs[0], total64 = seg_ofs[nseg] - first;
+    if (total64 > (int64_t)1 << 30) return fail(c, "cloud_filter: %lld points in one call > 2^30", (long long)total64);
+    if (nseg > 1 << 20) return fail(c, "cloud_filter: %d segments > 2^20", nseg);
+    const int total = (int)total64;
+    if (total && (!xyz || !out_keep)) return fail(c, "cloud_filter: null xyz / out_keep");
+    // one host pass: every coordinate finite (PCL's branch for the others is not restated), the box of every segment
+    std::vector<CfSeg> segs((size_t)nseg);
+    bool any = false;
+    for (int s = 0; s < nseg; ++s) {
+        CfSeg &g = segs[(size_t)s];
+        g.ofs = (int)(seg_ofs[s] - first); g.n = (int)(seg_ofs[s + 1] - seg_ofs[s]); g.pad = 0;
+        float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
+        const float *p = xyz + 3 * (size_t)seg_ofs[s];
+        for (int i = 0; i < g.n; ++i, p += 3) {
+            if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]))
+                return fail(c, "cloud_filter: point %d of segment %d has a non-finite coordinate", i, s);
+            for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], p[a]); mx[a] = std::max(mx[a], p[a]); }
+        }
+        float ext = 0.f;
+        for (int a = 0; a < 3; ++a) { g.mn[a] = g.n ? mn[a] : 0.f; if (g.n) ext = std::max(ext, mx[a] - mn[a]); }
+        g.inv_h = ext > 0.f ? 1024.0f / ext : 0.f;
+        if (!std::isfinite(g.inv_h)) g.inv_h = 0.f;
+        g.h = g.inv_h > 0.f ? 1.0f / g.inv_h : 0.f;
+        any = any || g.n >= mean_k + 1;
+    }
+    std::vector<float> md_own;
+    if (!out_mean_dist_or_null) md_own.resize((size_t)std::max(total, 1));
+    float *mdv = out_mean_dist_or_null ? out_mean_dist_or_null + first : md_own.data();       // mean distance of point seg_ofs[0] + i
+    if (!any) std::fill(mdv, mdv + total, 0.f);
+    else {
+        const size_t N = (size_t)total;
+        auto &f = c->cf;
+        if (cf_reserve(c, f.xyz, 12 * N) || cf_reserve(c, f.segs, sizeof(CfSeg) * (size_t)nseg) || cf_reserve(c, f.keys, 8 * N) || cf_reserve(c, f.keys2, 8 * N) ||
+            cf_reserve(c, f.vals, 4 * N) || cf_reserve(c, f.vals2, 4 * N) || cf_reserve(c, f.soa, 12 * N) || cf_reserve(c, f.out, 4 * N)) return -1;
+        if (!f.climbs) { HIPCHK(c, hipMalloc(&f.climbs, sizeof(unsigned))); }
+        int seg_bits = 1;
+        while ((1 << seg_bits) < nseg) ++seg_bits;
+        size_t tmp_bytes = 0;
+        HIPCHK(c, rocprim::radix_sort_pairs(nullptr, tmp_bytes, (unsigned long long *)f.keys.p, (unsigned long long *)f.keys2.p, (unsigned *)f.vals.p,
+                                            (unsigned *)f.vals2.p, N, 0u, (unsigned)(30 + seg_bits), c->stream));
+        if (cf_reserve(c, f.tmp, tmp_bytes)) return -1;
+        HIPCHK(c, hipMemcpy(f.xyz.p, xyz + 3 * (size_t)first, 12 * N, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(f.segs.p, segs.data(), sizeof(CfSeg) * (size_t)nseg, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemsetAsync(f.climbs, 0, sizeof(unsigned), c->stream));
+        float *sx = (float *)f.soa.p, *sy = sx + N, *sz = sy + N;
+        tm_begin(c, FAM_CF, total);
+        hipLaunchKernelGGL(k_cf_keys, cf_grid(total), dim3(CF_THREADS), 0, c->stream, (const float *)f.xyz.p, total, (const CfSeg *)f.segs.p, nseg,
+                           (unsigned long long *)f.keys.p, (unsigned *)f.vals.p);
+        HIPCHK(c, rocprim::radix_sort_pairs(f.tmp.p, tmp_bytes, (unsigned long long *)f.keys.p, (unsigned long long *)f.keys2.p, (unsigned *)f.vals.p,
+                                            (unsigned *)f.vals2.p, N, 0u, (unsigned)(30 + seg_bits), c->stream));
+        hipLaunchKernelGGL(k_cf_gather, cf_grid(total), dim3(CF_THREADS), 0, c->stream, (const float *)f.xyz.p, (const unsigned *)f.vals2.p, total, sx, sy, sz);
+        // 51 register slots hold the reference's k = 50; a larger k takes the 65-slot instance
+        if (mean_k <= 50)
+            hipLaunchKernelGGL(k_cf_knn<51>, cf_grid(total), dim3(CF_THREADS), 0, c->stream, (const unsigned long long *)f.keys2.p, (const unsigned *)f.vals2.p,
+                               (const float *)sx, (const float *)sy, (const float *)sz, total, (const CfSeg *)f.segs.p, mean_k, (float *)f.out.p, f.climbs);
+        else
+            hipLaunchKernelGGL(k_cf_knn<CF_KMAX + 1>, cf_grid(total), dim3(CF_THREADS), 0, c->stream, (const unsigned long long *)f.keys2.p, (const unsigned *)f.vals2.p,
+                               (const float *)sx, (const float *)sy, (const float *)sz, total, (const CfSeg *)f.segs.p, mean_k, (float *)f.out.p, f.climbs);
+        tm_end(c);
+        HIPCHK(c, hipGetLastError());
+        if (d2h_sync(c, 0, 0)) return -1;
+        HIPCHK(c, hipMemcpy(mdv, f.out.p, 4 * N, hipMemcpyDeviceToHost));
+        unsigned climbed = 0;
+        HIPCHK(c, hipMemcpy(&climbed, f.climbs, sizeof(unsigned), hipMemcpyDeviceToHost));
+        for (const CfSeg &g : segs) if (g.n >= mean_k + 1) f.queries += g.n;
+        f.climbed += climbed;
+    }
+    // PCL's statistics on the host, sequentially in index order: the threshold has the yardstick's bits by construction
+    for (int s = 0; s < nseg; ++s) {
+        const CfSeg &g = segs[(size_t)s];
+        const float *d = mdv + g.ofs;
+        uint8_t *keep = out_keep + seg_ofs[s];
+        if (g.n < mean_k + 1) {                            // no valid distance: 0 / 0, nothing is above a NaN
+            out_threshold[s] = std::nan("");
+            for (int i = 0; i < g.n; ++i) keep[i] = 1;
+            continue;
+        }
+        double sum = 0.0, sq_sum = 0.0;
+        for (int i = 0; i < g.n; ++i) { sum += (double)d[i]; const float sq = d[i] * d[i]; sq_sum += (double)sq; }
+        const double nv = (double)g.n, mean = sum / nv, var = (sq_sum - sum * sum / nv) / (nv - 1.0);
+        const double thr = mean + stddev_mul * std::sqrt(var);
+        out_threshold[s] = thr;
+        for (int i = 0; i < g.n; ++i) keep[i] = !((double)d[i] > thr) ? 1 : 0;
+    }
+    return 0;
+}
+
+int svslam_debug_cloud_sor_climbs(svslam_ctx *c, long long *out_queries, long long *out_climbed)
+{
+    if (!c) return -1;
+    if (out_queries) *out_queries = c->cf.queries;
+    if (out_climbed) *out_climbed = c->cf.climbed;
+    c->cf.queries = c->cf.climbed = 0;
+    return 0;
+}
+
+int svslam_cloud_voxel_grid(svslam_ctx *c, int64_t n, const float *xyz, const uint8_t *rgb, double leaf, float *out_xyz, uint8_t *out_rgb,
+                            int64_t *out_n, int *out_overflowed)
+{
+    if (!c) return -1;
+    if (!(leaf > 0) || !std::isfinite(leaf)) return fail(c, "cloud_filter: leaf %g must be positive", leaf);
+    if (n < 0 || n > (int64_t)1 << 30) return fail(c, "cloud_filter: %lld points out of [0, 2^30]", (long long)n);
+    if (!out_n || !out_overflowed) return fail(c, "cloud_filter: null out_n / out_overflowed");
+    *out_n = 0; *out_overflowed = 0;
+    if (n == 0) return 0;
+    if (!xyz || !rgb || !out_xyz || !out_rgb) return fail(c, "cloud_filter: null cloud / output");
+    const size_t N = (size_t)n;
+    float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for (size_t i = 0; i < N; ++i)
+        for (int a = 0; a < 3; ++a) {
+            const float v = xyz[3 * i + a];
+            if (!std::isfinite(v)) return fail(c, "cloud_filter: point %zu has a non-finite coordinate", i);
+            mn[a] = std::min(mn[a], v); mx[a] = std::max(mx[a], v);
+        }
+    VgParams P;
+    P.inv = 1.0f / (float)leaf;
+    if (!std::isfinite(P.inv) || !(P.inv > 0.f)) return fail(c, "cloud_filter: leaf %g has no float reciprocal", leaf);
+    // PCL's guard: more than INT32_MAX cells -> "Leaf size is too small for the input dataset", the output is the input
+    int64_t cells[3];
+    bool over = false;
+    for (int a = 0; a < 3; ++a) {
+        const float e = (mx[a] - mn[a]) * P.inv;
+        if (!(e < 9.0e18f)) over = true; else cells[a] = (int64_t)e + 1;
+    }
+    if (!over) over = (__int128)cells[0] * cells[1] * cells[2] > (__int128)INT32_MAX;
+    if (over) {
+        memcpy(out_xyz, xyz, 12 * N); memcpy(out_rgb, rgb, 3 * N);
+        *out_n = n; *out_overflowed = 1;
+        return 0;
+    }
+    int max_b[3], div_b[3];
+    for (int a = 0; a < 3; ++a) {
+        P.min_b[a] = (int)std::floor(mn[a] * P.inv); max_b[a] = (int)std::floor(mx[a] * P.inv);
+        div_b[a] = max_b[a] - P.min_b[a] + 1;
+    }
+    P.mul[0] = 1; P.mul[1] = div_b[0]; P.mul[2] = (int)((unsigned)div_b[0] * (unsigned)div_b[1]);
+    auto &f = c->cf;
+    if (cf_reserve(c, f.xyz, 12 * N) || cf_reserve(c, f.rgb, 3 * N) || cf_reserve(c, f.keys, 8 * N) || cf_reserve(c, f.keys2, 8 * N) || cf_reserve(c, f.flag, 4 * N) ||
+        cf_reserve(c, f.pos, 4 * N) || cf_reserve(c, f.start, 4 * N) || cf_reserve(c, f.oxyz, 12 * N) || cf_reserve(c, f.orgb, 3 * N)) return -1;
+    size_t sort_bytes = 0, scan_bytes = 0;
+    HIPCHK(c, rocprim::radix_sort_keys(nullptr, sort_bytes, (unsigned long long *)f.keys.p, (unsigned long long *)f.keys2.p, N, 0u, 64u, c->stream));
+    HIPCHK(c, rocprim::inclusive_scan(nullptr, scan_bytes, (unsigned *)f.flag.p, (unsigned *)f.pos.p, N, rocprim::plus<unsigned>(), c->stream));
+    if (cf_reserve(c, f.tmp, std::max(sort_bytes, scan_bytes))) return -1;
+    HIPCHK(c, hipMemcpy(f.xyz.p, xyz, 12 * N, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(f.rgb.p, rgb, 3 * N, hipMemcpyHostToDevice));
+    const int ni = (int)n;
+    tm_begin(c, FAM_CF, n);
+    hipLaunchKernelGGL(k_vg_keys, cf_grid(n), dim3(CF_THREADS), 0, c->stream, (const float *)f.xyz.p, ni, P, (unsigned long long *)f.keys.p);
+    HIPCHK(c, rocprim::radix_sort_keys(f.tmp.p, sort_bytes, (unsigned long long *)f.keys.p, (unsigned long long *)f.keys2.p, N, 0u, 64u, c->stream));
+    hipLaunchKernelGGL(k_vg_heads, cf_grid(n), dim3(CF_THREADS), 0, c->stream, (const unsigned long long *)f.keys2.p, ni, (unsigned *)f.flag.p);
+    HIPCHK(c, rocprim::inclusive_scan(f.tmp.p, scan_bytes, (unsigned *)f.flag.p, (unsigned *)f.pos.p, N, rocprim::plus<unsigned>(), c->stream));
+    hipLaunchKernelGGL(k_vg_starts, cf_grid(n), dim3(CF_THREADS), 0, c->stream, (const unsigned *)f.flag.p, (const unsigned *)f.pos.p, ni, (int *)f.start.p);
+    HIPCHK(c, hipGetLastError());
+    // the number of voxels decides the last launch: one small read-back in the middle of the call
+    unsigned m = 0;
+    HIPCHK(c, hipMemcpyAsync(&m, (unsigned *)f.pos.p + (N - 1), sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (m < 1 || (size_t)m > N) return fail(c, "cloud_filter: voxel count %u out of [1, %zu]", m, N);
+    hipLaunchKernelGGL(k_vg_reduce, cf_grid(m), dim3(CF_THREADS), 0, c->stream, (const unsigned long long *)f.keys2.p, (const int *)f.start.p, (int)m, ni,
+                       (const float *)f.xyz.p, (const uint8_t *)f.rgb.p, (float *)f.oxyz.p, (uint8_t *)f.orgb.p);
+    tm_end(c);
+    HIPCHK(c, hipGetLastError());
+    if (d2h_sync(c, 0, 0)) return -1;
+    HIPCHK(c, hipMemcpy(out_xyz, f.oxyz.p, 12 * (size_t)m, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out_rgb, f.orgb.p, 3 * (size_t)m, hipMemcpyDeviceToHost));
+    *out_n = (int64_t)m;
     return 0;
 }
 

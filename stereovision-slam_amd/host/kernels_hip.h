@@ -71,6 +71,11 @@ public:
     int dense_cloud(int n, svslam_dense_job *jobs, const double *cam_l, const double *ext_l, double baseline, const svslam_bm_params *p,
                     double min_depth, int max_pts_per_job, float *out_xyz, int *out_pix, int16_t *out_disp)
     { return svslam_dense_cloud_batch(ctx_, n, jobs, cam_l, ext_l, baseline, p, min_depth, max_pts_per_job, out_xyz, out_pix, out_disp); }
+    // the cloud filters of :175-209 (pcl::StatisticalOutlierRemoval on nseg clouds at once, pcl::VoxelGrid)
+    int cloud_sor(int nseg, const int64_t *seg_ofs, const float *xyz, int mean_k, double stddev_mul, uint8_t *out_keep, double *out_threshold)
+    { return svslam_cloud_sor_batch(ctx_, nseg, seg_ofs, xyz, mean_k, stddev_mul, out_keep, nullptr, out_threshold); }
+    int cloud_voxel_grid(int64_t n, const float *xyz, const uint8_t *rgb, double leaf, float *out_xyz, uint8_t *out_rgb, int64_t *out_n, int *out_overflowed)
+    { return svslam_cloud_voxel_grid(ctx_, n, xyz, rgb, leaf, out_xyz, out_rgb, out_n, out_overflowed); }
     int track(int n, svslam_track_job *jobs, const void *const *imgs, const int *strides, int is_device,
               int total, const double *cam, const float *prev_xy, float *next_xy, const uint8_t *has_mp,
               const double *xyz, uint8_t *status, uint8_t *outlier, const svslam_lk_params *p, double chi2_th)

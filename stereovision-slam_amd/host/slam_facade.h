@@ -545,8 +545,10 @@ private:
 // right_cam_index, output_dir), runs cv::StereoBM(128, 15) and the back-projection of every keyframe on the device
 // (svslam_dense_cloud_batch, several keyframes per call) and writes output_dir/dense_map.pcd.
 // Differences from the reference, all stated in DESIGN 9: the image reader is GREYSCALE (facade::imread), so r = g = b = the
-// grey value of the left pixel; PCL's StatisticalOutlierRemoval (k = 50) and the 2 cm VoxelGrid (:175-209) are not built, the
-// file holds the unfiltered merge of the keyframe clouds in keyframe order; the file goes to output_dir itself, not into a
+// grey value of the left pixel; PCL's StatisticalOutlierRemoval (k = 50, once per keyframe cloud and once on the merge) and the
+// 2 cm VoxelGrid (:175-209) run only with `cloud_filters: 1` in the dense config (svslam_cloud_sor_batch, svslam_cloud_voxel_grid;
+// their contract is tests/ref_cloud_filters.py) — the default 0 writes the unfiltered merge of the keyframe clouds in keyframe
+// order, as before the filters existed; the file goes to output_dir itself, not into a
 // time-stamped folder below it; as everywhere in this facade the 1/2 decimation of Dataset::FrameById happens on the device.
 struct DenseKeyframe { unsigned long image_id; SE3 T_cw; };
 
@@ -613,6 +615,7 @@ public:
         if (!dataset_->initialize()) throw SLAMException("Cannot initialize object to read dataset.");
         params_.num_disparities = num_disparities_; params_.block_size = blockSize_;
         params_.pre_filter_cap = 31; params_.texture_threshold = 10; params_.uniqueness_ratio = 15; params_.reserved = 0;
+        cloud_filters_ = (int)config_.Num("cloud_filters", 0) != 0;
         xyz_.clear(); grey_.clear();
     }
 
@@ -657,19 +660,69 @@ public:
             xyz.resize(3 * (size_t)cap * (size_t)nb); pix.resize((size_t)cap * (size_t)nb);
             if (kernels_->dense_cloud(nb, jobs.data(), cam, cl->pose.v, baseline, &params_, 1.0, cap, xyz.data(), pix.data(), nullptr) != 0)
                 throw SLAMException(std::string("DenseReconstruction: ") + kernels_->last_error());
+            // statistical_filter.filter(*tmp) of every keyframe cloud (:179-184): the call's keyframes are the segments of one batch
+            std::vector<uint8_t> keep;
+            if (cloud_filters_) {
+                std::vector<float> packed;
+                std::vector<int64_t> seg_ofs(1, 0);
+                for (int i = 0; i < nb; ++i) {
+                    const svslam_dense_job &j = jobs[(size_t)i];
+                    packed.insert(packed.end(), xyz.begin() + 3 * (long)j.pt_ofs, xyz.begin() + 3 * ((long)j.pt_ofs + j.n_points));
+                    seg_ofs.push_back(seg_ofs.back() + j.n_points);
+                }
+                keep.assign((size_t)seg_ofs.back() + 1, 1);
+                std::vector<double> thr((size_t)nb);
+                if (kernels_->cloud_sor(nb, seg_ofs.data(), packed.data(), 50, 1.0, keep.data(), thr.data()) != 0)
+                    throw SLAMException(std::string("DenseReconstruction: ") + kernels_->last_error());
+            }
+            size_t kpos = 0;
             for (int i = 0; i < nb; ++i) {
                 const svslam_dense_job &j = jobs[(size_t)i];
                 const Image &src = frames[(size_t)i]->left_img_;
-                xyz_.insert(xyz_.end(), xyz.begin() + 3 * (long)j.pt_ofs, xyz.begin() + 3 * ((long)j.pt_ofs + j.n_points));
-                for (int p = 0; p < j.n_points; ++p) {
-                    const int y = pix[(size_t)j.pt_ofs + (size_t)p] / w_, x = pix[(size_t)j.pt_ofs + (size_t)p] - y * w_;
+                for (int p = 0; p < j.n_points; ++p, ++kpos) {
+                    if (cloud_filters_ && !keep[kpos]) continue;
+                    const size_t o = (size_t)j.pt_ofs + (size_t)p;
+                    xyz_.insert(xyz_.end(), xyz.begin() + 3 * (long)o, xyz.begin() + 3 * (long)o + 3);
+                    const int y = pix[o] / w_, x = pix[o] - y * w_;
                     grey_.push_back(src.data[(size_t)(2 * y) * (size_t)src_w_ + (size_t)(2 * x)]);     // dst(x, y) = src(2x, 2y) (src/dataset.cpp:162-165)
                 }
             }
         }
+        if (cloud_filters_ && !grey_.empty()) FilterMergedCloud();
         const std::string output_dir = config_.Str("output_dir", ".");
         map_file_ = output_dir + "/dense_map.pcd";
         if (!SavePCDFileBinary(map_file_)) throw SLAMException("DenseReconstruction: cannot write " + map_file_);
+    }
+
+    // :190-209 — the outlier removal once more on the merged cloud, then the 2 cm voxel grid.  grey goes through the grid as
+    // r = g = b; the three sums of a voxel are the same sum, so the centroid's colour is grey again.
+    void FilterMergedCloud()
+    {
+        const int64_t n = (int64_t)grey_.size();
+        const int64_t seg_ofs[2] = { 0, n };
+        std::vector<uint8_t> keep((size_t)n);
+        double thr = 0;
+        if (kernels_->cloud_sor(1, seg_ofs, xyz_.data(), 50, 1.0, keep.data(), &thr) != 0)
+            throw SLAMException(std::string("DenseReconstruction: ") + kernels_->last_error());
+        std::vector<float> fx;
+        std::vector<uint8_t> frgb;
+        for (size_t i = 0; i < (size_t)n; ++i) {
+            if (!keep[i]) continue;
+            fx.insert(fx.end(), xyz_.begin() + 3 * (long)i, xyz_.begin() + 3 * (long)i + 3);
+            frgb.insert(frgb.end(), 3, grey_[i]);
+        }
+        const int64_t nf = (int64_t)(frgb.size() / 3);
+        std::vector<float> ox(3 * (size_t)nf + 3);
+        std::vector<uint8_t> orgb(3 * (size_t)nf + 3);
+        int64_t m = 0;
+        int overflowed = 0;
+        const double resolution = 0.02;
+        if (kernels_->cloud_voxel_grid(nf, fx.data(), frgb.data(), resolution, ox.data(), orgb.data(), &m, &overflowed) != 0)
+            throw SLAMException(std::string("DenseReconstruction: ") + kernels_->last_error());
+        if (overflowed) std::fprintf(stderr, "[pcl::VoxelGrid::applyFilter] Leaf size is too small for the input dataset. Integer indices would overflow.\n");
+        xyz_.assign(ox.begin(), ox.begin() + 3 * (long)m);
+        grey_.resize((size_t)m);
+        for (size_t i = 0; i < (size_t)m; ++i) grey_[i] = orgb[3 * i];
     }
 
     // pcl::io::savePCDFileBinary of a PointXYZRGB cloud: PCD v0.7, x y z rgb, the colour packed r << 16 | g << 8 | b into the
@@ -712,6 +765,7 @@ private:
     ConfigFile config_;
     int left_cam_index_ = 0, right_cam_index_ = 1, left_camera_index_in_slam_ = 0;
     int num_disparities_ = 128, blockSize_ = 15;   // include/StereoVisionSLAM/dense_reconstruction.h:56-57
+    bool cloud_filters_ = false;                   // dense config `cloud_filters`: the PCL filters of :175-209
     svslam_bm_params params_;
     std::vector<DenseKeyframe> keyframes_;
     Dataset::Ptr dataset_;
