@@ -489,6 +489,13 @@ int svslam_debug_ll_shards(svslam_ctx *ctx, int nproblems, int *out8, int *shard
 /* test hook: the low-latency solver's residency guard (svslam_set_low_latency): shards per problem (0 = batch solver only),
  * problems one call may hand to it, CUs counted, co-resident solver workgroups per CU                                      */
 int svslam_debug_ll_limits(svslam_ctx *ctx, int *out4);
+/* test hook: the descriptors of the last svslam_local_ba_batch / svslam_local_ba_collect as the solver returned them, 8 ints per
+ * problem: blocks, active poses, block pairs, LDS tiles, landmarks that go through the tiles, iterations, LM trials, flags
+ * (bit 0: the edges arrived landmark-major with keyframes ascending, bit 1: the device build read them through its LDS edge
+ * cache — the argument its last launch was given, bit 2: the structure was built on the host, SVSLAM_BA_HOST_BUILD).  `njobs`
+ * must be that call's problem count.  Meant for calls the batch solver took: after a low-latency call the problems' own
+ * descriptors carry no block, tile or pose counts (svslam_debug_ll_shards has the shards').                               */
+int svslam_debug_ba_struct(svslam_ctx *ctx, int njobs, int *out8);
 int svslam_debug_clock_mhz(svslam_ctx *ctx, int blocks, double ms, double *mhz);
 /* test hook: `ncus` workgroups that each take one CU's whole LDS and spin for `ms` milliseconds, enqueued on the context's stream
  * (asynchronous; svslam_sync waits): those CUs cannot take a workgroup that needs LDS meanwhile.  What it shows

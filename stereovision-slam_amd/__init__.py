@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "svslam_device_count", "svslam_dmap_keyframe_batch", "svslam_dmap_ba_collect", "svslam_dmap_read", "svslam_dmap_evicted", "svslam_sba_comm_unique_id", "svslam_sba_comm_init", "svslam_sba_comm_destroy", "svslam_sba_solve",
     "svslam_dev_alloc", "svslam_dev_free", "svslam_dev_upload", "svslam_dev_download", "svslam_sync",
     "svslam_timing_enable", "svslam_timing_reset", "svslam_timing_get", "svslam_ba_profile",
-    "svslam_set_host_threads", "svslam_debug_host_ns", "svslam_debug_ll_shards", "svslam_debug_ll_limits", "svslam_debug_clock_mhz", "svslam_debug_hold_cus", "svslam_lm_trace",
+    "svslam_set_host_threads", "svslam_debug_host_ns", "svslam_debug_ll_shards", "svslam_debug_ll_limits", "svslam_debug_ba_struct", "svslam_debug_clock_mhz", "svslam_debug_hold_cus", "svslam_lm_trace",
 ]
 
 FAMILIES = {"pyramid": 0, "lk": 1, "gftt": 2, "triangulate": 3, "pose_only": 4, "local_ba": 5}
@@ -250,6 +250,15 @@ class Context:
         out = np.zeros((nproblems * 16, 8), np.int32)
         self._chk(self.L.svslam_debug_ll_shards(self.h, nproblems, _p(out), C.byref(w)), "debug_ll_shards")
         return out[:nproblems * w.value].reshape(nproblems, w.value, 8).copy()
+
+    BA_STRUCT_FIELDS = ("nblk", "na", "ncontrib", "ntile", "nmv", "iters_done", "ntrial", "flags")
+
+    def ba_struct(self, njobs=1):
+        """test hook (svslam_debug_ba_struct): [njobs, 8] ints of the last local-BA call — blocks, active poses, block pairs,
+        tiles, landmarks in the tiles, iterations, LM trials, flags (1 edges arrived in order, 2 edge cache used, 4 host build)"""
+        out = np.zeros((njobs, 8), np.int32)
+        self._chk(self.L.svslam_debug_ba_struct(self.h, njobs, _p(out)), "debug_ba_struct")
+        return out
 
     def low_latency(self, on=True):
         """latency shape of the serial kernels (svslam_set_low_latency): a few jobs per launch"""

@@ -145,6 +145,7 @@ struct BaHostStruct {        // scratch reused across jobs
         act_kf, tile_lm, pcs, pitem, fill, bpa, lkf, sv_start, blk_es;
     std::vector<BaRec> recs;     // [0,nobs) landmark-major (= lm_edges order), [nobs,2nobs) pose-major
     int nblk = 0, na = 0, ncontrib = 0, ntile = 0, nmv = 0;
+    bool in_order = true;        // the edges of the last build() arrived landmark-major, keyframes ascending (svslam_debug_ba_struct)
 
     // Returns false if an edge index is out of range.  Two passes over the edges when they
     // arrive landmark-major with keyframes ascending inside a landmark (the order the host
@@ -162,6 +163,7 @@ struct BaHostStruct {        // scratch reused across jobs
             if (k < 0 || k >= nkf || l < 0 || l >= nlm) return false;
             if (e && !((olm[e - 1] < l) || (olm[e - 1] == l && okf[e - 1] <= k))) sorted = false;
         }
+        in_order = sorted;
         srt.resize(nobs);
         for (int e = 0; e < nobs; ++e) srt[e] = e;
         if (!sorted)

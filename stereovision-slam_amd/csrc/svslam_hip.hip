@@ -155,6 +155,11 @@ struct svslam_ctx {
              // what a repeat with the batch solver needs when the low-latency solver gives up (svslam_local_ba_collect)
              bool ll_used = false; size_t ocams = 0, opk = 0, ouv = 0, osrt = 0, orecs = 0, oaux = 0, out_end = 0; int max_nlm = 0, max_nobs = 0, iters = 0;
              double delta = 0; } ba_pending;
+    // svslam_debug_ba_struct reads these: the descriptors the last collected batch came back with, the edge_cache argument the
+    // last k_ba_build launch got, and (host build only) whether each problem's edges arrived in order
+    std::vector<BaDev> ba_last;
+    int ba_last_ec = 0;
+    std::vector<unsigned char> ba_host_in_order;
     // an open shared-map BA problem (svslam_sba_*): this rank's shard lives in the arena like a submitted batch
     struct { bool open = false; int nkf = 0, nlm = 0, nobs = 0, np = 0; size_t ojobs = 0, ocams = 0, oposes = 0, opts = 0, orecs = 0,
              oaux = 0, ochi = 0, oio = 0; double delta = 0; int launches = 0; } sba;
@@ -322,6 +327,7 @@ void launch_ba_solver(svslam_ctx *c, int njobs, bool ll, BaDev *jobs, const BaCa
     const bool tms = time_solver && !split_timing;
     const int tile_cap = ll ? ba_ll_tile_cap(c) : ba_tile_cap(c->lim.max_kf);
     const int ec = bb_edge_cache_fits(max_nlm, max_nobs) ? 1 : 0;
+    c->ba_last_ec = ec;                        // what k_ba_build is told below (svslam_debug_ba_struct reports it)
     if (!ll) {
         hipLaunchKernelGGL(k_ba_build, dim3(njobs), dim3(BB_THREADS), bb_lds_bytes(max_nlm, max_nobs), c->stream, jobs, packed, uv, srt, recs, aux,
                            tile_cap, max_nlm, flag, 0, ec, 0);
@@ -1592,6 +1598,7 @@ int svslam_local_ba_submit(svslam_ctx *c, int njobs, const svslam_ba_job *jobs, 
     int max_nlm = 1, max_nobs = 1;
     bool all_sorted = true;
     if (c->ba_host_build) {
+        c->ba_host_in_order.assign((size_t)njobs, 0);
         // Host-side structure of every problem (edge records, blocks, pose-pair lists), built by the
         // pool with one scratch structure per thread (stays cache-hot) and written straight into the
         // arena; the aux space of a problem comes from a bump allocator, so its position depends on
@@ -1612,6 +1619,7 @@ int svslam_local_ba_submit(svslam_ctx *c, int njobs, const svslam_ba_job *jobs, 
             hs.write(bj, aux + at, recs + 2 * (size_t)bj.obs_ofs, dj[i]);
             dj[i].aux_ofs = (int)at;
             dj[i].rec_ofs = 2 * bj.obs_ofs;
+            c->ba_host_in_order[(size_t)i] = hs.in_order ? 1 : 0;
         };
         if (c->pool && njobs > 1) c->pool->parallel_for(njobs, build_one);
         else for (int i = 0; i < njobs; ++i) build_one(i);
@@ -1727,7 +1735,8 @@ int svslam_local_ba_collect(svslam_ctx *c, int njobs, svslam_ba_job *jobs, int t
     const BaDev *dj = hp<BaDev>(c, c->ba_pending.ojobs);
     std::vector<int> bad;
     for (int i = 0; i < njobs; ++i) if (dj[i].iters_done < 0) bad.push_back(i);
-    std::vector<BaDev> res(dj, dj + njobs);        // descriptors as the first solve returned them
+    std::vector<BaDev> &res = c->ba_last;          // descriptors as the first solve returned them (kept for svslam_debug_ba_struct)
+    res.assign(dj, dj + njobs);
     if (!bad.empty()) {
         // a shard of the low-latency solver never became resident.  A problem that gives up writes nothing back, so ITS inputs are
         // untouched in the device arena; the problems that finished have their results there already (poses and positions are
@@ -2499,6 +2508,24 @@ int svslam_debug_ll_shards(svslam_ctx *c, int nproblems, int *out8, int *shards_
     for (size_t i = 0; i < h.size(); ++i) {
         int *o = out8 + 8 * i;
         o[0] = h[i].nlm; o[1] = h[i].nobs; o[2] = h[i].nblk; o[3] = h[i].ntile; o[4] = h[i].reserved; o[5] = h[i].na; o[6] = h[i].shmask; o[7] = h[i].iters_done;
+    }
+    return 0;
+}
+
+// test hook: the problem descriptors of the last svslam_local_ba_batch / _collect as the batch solver returned them, 8 ints per
+// problem — blocks, active poses, block pairs, tiles, landmarks in the tiles (nmv), iterations, LM trials, flags (bit 0: the edges
+// arrived landmark-major with keyframes ascending; bit 1: the edge_cache argument of the last k_ba_build launch; bit 2: structure
+// built on the host).  After a call the low-latency solver took, the counts are those of the parents' descriptors, which carry
+// none but iterations, trials and block pairs: use svslam_debug_ll_shards there.
+int svslam_debug_ba_struct(svslam_ctx *c, int njobs, int *out8)
+{
+    if (njobs < 1 || (size_t)njobs != c->ba_last.size()) return fail(c, "debug_ba_struct: the last local-BA call had %zu problems, not %d", c->ba_last.size(), njobs);
+    for (int i = 0; i < njobs; ++i) {
+        const BaDev &d = c->ba_last[(size_t)i];
+        int *o = out8 + 8 * (size_t)i;
+        o[0] = d.nblk; o[1] = d.na; o[2] = d.ncontrib; o[3] = d.ntile; o[4] = d.nmv; o[5] = d.iters_done; o[6] = d.ntrial;
+        if (c->ba_host_build) o[7] = 4 | ((size_t)i < c->ba_host_in_order.size() && c->ba_host_in_order[(size_t)i] ? 1 : 0);
+        else o[7] = (d.reserved ? 1 : 0) | (c->ba_last_ec ? 2 : 0);      // (reserved: the host's in-order mark, which the batch kernels leave alone)
     }
     return 0;
 }

@@ -1,5 +1,6 @@
 """shared helpers for tests: seeded synthetic scenes and BA problems."""
 import importlib
+import os
 
 import numpy as np
 
@@ -27,6 +28,29 @@ GENERAL_RIG = ((359.428, 371.9, 303.5964, 92.60785), _ext((0.01, -0.02, 0.015), 
 
 def pkg():
     return importlib.import_module("stereovision-slam_amd")
+
+
+LL_CTX_KW = dict(max_slots=1, max_jobs=16, max_kf=11, max_lm=4096, max_obs=16384)
+
+
+def make_ll_ctx(svs, shards, resident):
+    """a low-latency context with `shards` workgroups per problem and the LM trace on.  resident = 1: problems whose shards all
+    fit LDS go to k_ba_ll, the others to k_local_ba_t<2>; 0: all to the latter"""
+    old = {k: os.environ.get(k) for k in ("SVSLAM_LL_SHARDS", "SVSLAM_LL_RESIDENT")}
+    os.environ["SVSLAM_LL_SHARDS"] = str(shards)
+    os.environ["SVSLAM_LL_RESIDENT"] = str(resident)
+    try:
+        c = svs.Context(W, H, **LL_CTX_KW)
+        c.low_latency(True)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    c.lm_trace(True)
+    c.resident = resident
+    return c
 
 
 def textured(rng, h, w, sigma=2.0):
@@ -72,15 +96,8 @@ def make_ba_problem(rng, nkf=7, nlm=300, noise=0.5, outlier_frac=0.05, pose_nois
     """synthetic local-BA problem: keyframes moving forward, landmarks in front,
     left+right observations; returns dict with truth and perturbed initial values.
     rig = (cam_l, ext_l, cam_r, ext_r) projects and decides visibility; None is KITTI_RIG."""
-    from scipy.spatial.transform import Rotation
     cam_l, ext_l, cam_r, ext_r = KITTI_RIG if rig is None else rig
-    poses = []
-    for k in range(nkf):
-        Rwc = Rotation.from_rotvec([0.01 * rng.normal(), 0.03 * k + 0.01 * rng.normal(), 0.01 * rng.normal()])
-        C = np.array([0.2 * np.sin(0.5 * k), 0.02 * rng.normal(), 0.9 * k])
-        Rcw = Rwc.inv()
-        poses.append(np.concatenate([Rcw.as_quat(), -Rcw.apply(C)]))
-    poses = np.array(poses)
+    poses = _ba_trajectory(rng, nkf)
     pts = np.stack([rng.uniform(-8, 8, nlm), rng.uniform(-3, 1.5, nlm), rng.uniform(6, 45, nlm) + 0.4 * nkf], 1)
     okf, olm, ori, ouv = [], [], [], []
     for k in range(nkf):
@@ -98,14 +115,80 @@ def make_ba_problem(rng, nkf=7, nlm=300, noise=0.5, outlier_frac=0.05, pose_nois
     ouv = np.array(ouv, np.float32)
     p = rng.permutation(len(okf))
     okf, olm, ori, ouv = okf[p], olm[p], ori[p], ouv[p]
-    poses0 = poses.copy()
+    poses0, pts0 = _ba_perturb(rng, poses, pts, pose_noise, pt_noise)
+    return dict(poses=poses, pts=pts, poses0=poses0, pts0=pts0, okf=okf, olm=olm, ori=ori, ouv=ouv)
+
+
+def make_ba_problem_vis(rng, vis_l, vis_r, noise=0.5, outlier_frac=0.05, pose_noise=0.02, pt_noise=0.05, rig=None):
+    """make_ba_problem with a PRESCRIBED visibility: vis_l, vis_r are boolean [nkf, nlm], the edge set is exactly those masks.
+    Same trajectory, cameras, measurement noise and perturbation; the landmarks are drawn (and redrawn) where both cameras
+    of every keyframe see them, so every prescribed edge is one the rig could have measured."""
+    cam_l, ext_l, cam_r, ext_r = KITTI_RIG if rig is None else rig
+    vis = (np.asarray(vis_l, bool), np.asarray(vis_r, bool))
+    nkf, nlm = vis[0].shape
+    assert vis[1].shape == (nkf, nlm)
+    poses = _ba_trajectory(rng, nkf)
+    views = [(poses[k], cam, ext) for k in range(nkf) for cam, ext in ((cam_l, ext_l), (cam_r, ext_r))]
+
+    def seen_by_all(P):
+        ok = np.ones(len(P), bool)
+        for T, cam, ext in views:
+            uv, z = project(cam, T, ext, P)
+            ok &= (z > 0.5) & (uv[:, 0] >= 0) & (uv[:, 0] < W) & (uv[:, 1] >= 0) & (uv[:, 1] < H)
+        return ok
+    pts = np.zeros((0, 3))
+    for _ in range(200):
+        if len(pts) >= nlm:
+            break
+        n = 4 * nlm + 64
+        P = np.stack([rng.uniform(-8, 8, n), rng.uniform(-3, 1.5, n), rng.uniform(6, 45, n) + 0.4 * nkf], 1)
+        pts = np.concatenate([pts, P[seen_by_all(P)]])
+    pts = pts[:nlm]
+    assert len(pts) == nlm and seen_by_all(pts).all(), "no room in the intersection of the frusta"
+    okf, olm, ori, ouv = [], [], [], []
     for k in range(nkf):
+        for cam_i, (cam, ext) in enumerate(((cam_l, ext_l), (cam_r, ext_r))):
+            idx = np.nonzero(vis[cam_i][k])[0]
+            uv, _ = project(cam, poses[k], ext, pts[idx])
+            m = uv + rng.normal(0, noise, (len(idx), 2))
+            out = rng.random(len(idx)) < outlier_frac
+            m[out] += rng.normal(0, 25, (int(out.sum()), 2))
+            okf += [k] * len(idx); olm += list(idx); ori += [cam_i] * len(idx); ouv += list(m)
+    okf = np.array(okf, np.int32); olm = np.array(olm, np.int32); ori = np.array(ori, np.uint8)
+    ouv = np.array(ouv, np.float32).reshape(-1, 2)
+    p = rng.permutation(len(okf))
+    okf, olm, ori, ouv = okf[p], olm[p], ori[p], ouv[p]
+    for cam_i in (0, 1):                                   # the realised edge set is the mask, each edge once
+        got = np.zeros((nkf, nlm), np.int64)
+        np.add.at(got, (okf[ori == cam_i], olm[ori == cam_i]), 1)
+        assert np.array_equal(got, vis[cam_i].astype(np.int64))
+    poses0, pts0 = _ba_perturb(rng, poses, pts, pose_noise, pt_noise)
+    return dict(poses=poses, pts=pts, poses0=poses0, pts0=pts0, okf=okf, olm=olm, ori=ori, ouv=ouv)
+
+
+def _ba_trajectory(rng, nkf):
+    """keyframes moving forward and turning slowly: T_cw as x y z w, t"""
+    from scipy.spatial.transform import Rotation
+    poses = []
+    for k in range(nkf):
+        Rwc = Rotation.from_rotvec([0.01 * rng.normal(), 0.03 * k + 0.01 * rng.normal(), 0.01 * rng.normal()])
+        C = np.array([0.2 * np.sin(0.5 * k), 0.02 * rng.normal(), 0.9 * k])
+        Rcw = Rwc.inv()
+        poses.append(np.concatenate([Rcw.as_quat(), -Rcw.apply(C)]))
+    return np.array(poses)
+
+
+def _ba_perturb(rng, poses, pts, pose_noise, pt_noise):
+    """initial values: every pose rotated and shifted, every landmark shifted"""
+    from scipy.spatial.transform import Rotation
+    poses0 = poses.copy()
+    for k in range(len(poses)):
         dq = Rotation.from_rotvec(rng.normal(0, pose_noise * 0.3, 3))
         q = (dq * Rotation.from_quat(poses[k, :4])).as_quat()
         poses0[k, :4] = q
         poses0[k, 4:] = dq.apply(poses[k, 4:]) + rng.normal(0, pose_noise, 3)
     pts0 = pts + rng.normal(0, pt_noise, pts.shape)
-    return dict(poses=poses, pts=pts, poses0=poses0, pts0=pts0, okf=okf, olm=olm, ori=ori, ouv=ouv)
+    return poses0, pts0
 
 
 def ba_job(p, keep=None, sort=False):

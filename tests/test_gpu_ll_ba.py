@@ -3,7 +3,6 @@ svslam_set_low_latency) — against the same oracle answers, at the same toleran
 (tests/test_gpu_lm_parity.py), for 4 / 8 / 16 shards; plus what only this path has: shards without edges, a
 problem smaller than its shard count, keyframes no shard sees, several problems per call.
 Backend::Optimize, reference src/backend.cpp:22-164.  All through the C ABI."""
-import os
 
 import numpy as np
 import pytest
@@ -22,23 +21,7 @@ def _sorted_job(job):
     return poses, pts, okf[o], olm[o], ori[o], ouv[o]
 
 
-def _make_ctx(svs, shards, resident):
-    """resident = 1: problems whose shards all fit LDS go to k_ba_ll, the others to k_local_ba_t<2>; 0: all to the latter"""
-    old = {k: os.environ.get(k) for k in ("SVSLAM_LL_SHARDS", "SVSLAM_LL_RESIDENT")}
-    os.environ["SVSLAM_LL_SHARDS"] = str(shards)
-    os.environ["SVSLAM_LL_RESIDENT"] = str(resident)
-    try:
-        c = svs.Context(cm.W, cm.H, max_slots=1, max_jobs=16, max_kf=11, max_lm=4096, max_obs=16384)
-        c.low_latency(True)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    c.lm_trace(True)
-    c.resident = resident
-    return c
+_make_ctx = cm.make_ll_ctx        # (test_gpu_general_rig.py imports it under this name)
 
 
 @pytest.fixture(scope="module", params=[(16, 1), (16, 0), (8, 1), (4, 0)], ids=lambda p: "%dshards-%s" % (p[0], "resident" if p[1] else "streaming"))
