@@ -313,6 +313,44 @@ int svslam_local_ba_collect(svslam_ctx *ctx, int njobs, svslam_ba_job *jobs,
                             int total_kf, double *poses, int total_lm, double *pts,
                             int total_obs, double *edge_chi2);
 
+/* ---- global pose-graph optimisation --------------------------------------------
+ * Replaces the g2o problem of LoopClosure::PoseGraphOptimization (src/loopclosure.cpp:641-799: VertexPose per keyframe,
+ * keyframe 0 fixed :701-704; EdgePoseGraph per odometry edge :720-735 and per loop edge :738-753, identity information, no
+ * robust kernel; optimize(22) :758 under OptimizationAlgorithmLevenberg over LinearSolverDense :662-673) and the landmark
+ * re-anchoring that follows it (:760-784).  One job is one graph: nkf vertices (SE(3) as everywhere here, ascending keyframe id)
+ * and nedge edges (a, b, M) with residual log(M^-1 T_a T_b^-1) (g2o_types.h:247-262; Sophus' 6-vector, translation first;
+ * formed as M^-1 (T_a T_b^-1): an odometry edge whose M is the host's T_a * T_b^-1 has residual exactly 0, so a graph without
+ * loop edges returns its input bits) and update T <- exp(d) T (VertexPose::oplusImpl, g2o_types.h:42-49).  Vertices with
+ * fixed[i] != 0 are constant.  LM control flow:
+ * g2o's, exactly as svslam_local_ba_batch has it.  After the last iteration point p with anchor vertex k >= 0 becomes
+ * T_k,new^-1 (T_k,old p) in f64 (also in a job without edges, where it is the identity up to rounding); anchor -1: untouched.
+ * The reference hands g2o a dense 6N x 6N system ("Takes seconds to minutes", :655); here the system is never formed: with the
+ * vertices in ascending id H is block tridiagonal plus one block per loop edge, and a block-skyline LDL^T (one wavefront per
+ * job) factorises it inside each row's envelope.  Declared deviations: closed-form Jacobians where g2o differentiates
+ * this edge numerically; an unpivoted factorisation where Eigen's dense Cholesky is used.
+ * Errors, nothing written: an edge index outside [0, nkf); a == b; a job with vertices but none fixed; a job with edges but
+ * no vertices; a job with more than 2^31 / 42 free vertices; jobs whose kf / edge / pt ranges do not ascend from job to job or overlap (gaps are allowed); a pose or measurement
+ * quaternion whose squared norm is further than 2e-6 from 1; an anchor outside [-1, nkf); no memory for the solver scratch
+ * (allocated inside the call on demand and kept; svslam_limits has no say in it, njobs is not bounded by max_jobs).
+ * Valid no-ops: a job with nkf == 0 or nedge == 0 (poses as given, iters_done = n_trials = 0, chi2 = 0).
+ * A job's result does not depend on the other jobs of the call, and two calls on the same inputs give the same bits.
+ * svslam_lm_trace records the trials of jobs 0 .. max_jobs - 1 of this call in its six-double format.             */
+typedef struct svslam_pg_job {
+    int kf_ofs, nkf;        /* vertices, ascending keyframe id */
+    int edge_ofs, nedge;
+    int pt_ofs, npt;        /* landmarks to re-anchor; npt may be 0 */
+    int iters_done;         /* out */
+    int n_trials;           /* out: accepted + rejected */
+    double chi2_before, chi2_after;   /* out */
+} svslam_pg_job;
+
+int svslam_pose_graph_batch(svslam_ctx *ctx, int njobs, svslam_pg_job *jobs,
+                            int total_kf, double *poses /* in/out, 7 each */, const uint8_t *fixed,
+                            int total_edges, const int *edge_a, const int *edge_b /* local to the job */,
+                            const double *edge_meas /* 7 each */,
+                            int total_pts, const int *pt_anchor /* local vertex or -1 */, double *pts /* in/out */,
+                            int iters);
+
 /* ---- shared-map bundle adjustment (BASELINE config 5; not in the reference) -----------
  * ONE local-BA problem whose landmarks are sharded over the GPUs of a node: every rank holds all
  * nkf poses and its landmarks with their edges.  The rank opens its shard, then runs the pieces of
@@ -352,7 +390,7 @@ int svslam_sba_solve(svslam_ctx *ctx, int iters, int *iters_done, double *lambda
  * and clears them.                                                            */
 int svslam_ba_profile(svslam_ctx *ctx, int enable, long long *out12);
 
-/* test hook: the Levenberg-Marquardt trajectory of the last svslam_pose_only_batch / svslam_local_ba_batch call
+/* test hook: the Levenberg-Marquardt trajectory of the last svslam_pose_only_batch / svslam_local_ba_batch / svslam_pose_graph_batch call
  * on this context — one record of 6 doubles per LM trial, rejected trials included: iteration (pose-only:
  * 16 round + iteration), lambda of the trial, chi2 before, chi2 of the trial state, rho, accepted.  enable = 1
  * allocates the device buffer (kernels record while it exists), 0 frees it; out != NULL reads job `job`.    */
@@ -515,7 +553,7 @@ int svslam_sync(svslam_ctx *ctx);
  * Accumulated per kernel family since the last reset; used by bench.py for
  * the roofline entry.  family: 0 pyramid, 1 lk, 2 gftt, 3 triangulate,
  * 4 pose_only, 5 local_ba, 6 stereo_bm (units = jobs), 12 cloud_filter (units = points; appended
- * after the last number in use, nothing moved).
+ * after the last number in use, nothing moved), 13 pose_graph (units = jobs; appended after 12, nothing moved).
  * Development families follow and are NOT stable numbers: with stereo_bm taking 6, the
  * per-kernel split moved from 6-9 to 7-10 and the local-BA solver interval from 10 to 11.
  * A caller that passed those raw numbers must move with them (Python addresses them by name). */

@@ -20,7 +20,7 @@ ABI_SYMBOLS = [
     "svslam_create", "svslam_destroy", "svslam_last_error", "svslam_build_info",
     "svslam_pyramid_batch", "svslam_pyramid_decimate_batch", "svslam_set_source_size", "svslam_set_low_latency", "svslam_set_pose_only_xtol", "svslam_get_pose_only_xtol", "svslam_pyramid_read",
     "svslam_pyramid_read_padded", "svslam_stereo_bm_batch", "svslam_stereo_bm_strip_rows", "svslam_dense_cloud_batch", "svslam_cloud_sor_batch", "svslam_cloud_voxel_grid", "svslam_debug_cloud_sor_climbs", "svslam_lk_batch", "svslam_gftt_batch", "svslam_gftt_eigmap", "svslam_triangulate_batch",
-    "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect",
+    "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect", "svslam_pose_graph_batch",
     "svslam_track_batch", "svslam_rtrack_batch", "svslam_rtrack_upload",
     "svslam_sba_io_doubles", "svslam_sba_open", "svslam_sba_phase", "svslam_sba_close",
     "svslam_device_count", "svslam_dmap_keyframe_batch", "svslam_dmap_ba_collect", "svslam_dmap_read", "svslam_dmap_evicted", "svslam_sba_comm_unique_id", "svslam_sba_comm_init", "svslam_sba_comm_destroy", "svslam_sba_solve",
@@ -36,11 +36,13 @@ DEBUG_FAMILIES = {"dbg0": 7, "dbg1": 8, "dbg2": 9, "dbg3": 10}     # per-kernel 
 # inside "local_ba" (= map gather + structure build + solver + scatter)
 KERNEL_FAMILIES = {"ba_solve": 11}
 CLOUD_FAMILIES = {"cloud_filter": 12}      # the outlier removal and the voxel grid of the dense program (units = points); appended, nothing renumbered
+LOOP_FAMILIES = {"pose_graph": 13}         # svslam_pose_graph_batch (units = jobs); appended after 12, nothing renumbered
 # the HIP kernel(s) behind each timing family at the batch operating point (what a rocprofv3 --kernel-trace --stats row is named)
 FAMILY_KERNELS = {"pyramid": ["k_pyr_fused"], "lk": ["k_lk"], "gftt": ["k_gftt_eig3", "k_gftt_select2"], "triangulate": ["k_triangulate"],
                   "pose_only": ["k_pose_only"], "local_ba": ["k_dmap_ba_gather", "k_ba_build", "k_local_ba_t", "k_dmap_ba_scatter"],
                   "ba_solve": ["k_local_ba_t"], "stereo_bm": ["k_bm_fill", "k_stereo_bm", "k_dense_cloud"],
-                  "cloud_filter": ["k_cf_keys", "k_cf_gather", "k_cf_knn", "k_vg_keys", "k_vg_heads", "k_vg_starts", "k_vg_reduce"]}
+                  "cloud_filter": ["k_cf_keys", "k_cf_gather", "k_cf_knn", "k_vg_keys", "k_vg_heads", "k_vg_starts", "k_vg_reduce"],
+                  "pose_graph": ["k_pose_graph"]}
 
 
 class Limits(C.Structure):
@@ -80,6 +82,12 @@ class PoseJob(C.Structure):
 class BaJob(C.Structure):
     _fields_ = [("kf_ofs", C.c_int), ("nkf", C.c_int), ("lm_ofs", C.c_int), ("nlm", C.c_int),
                 ("obs_ofs", C.c_int), ("nobs", C.c_int), ("iters_done", C.c_int), ("reserved", C.c_int)]
+
+
+class PgJob(C.Structure):
+    _fields_ = [("kf_ofs", C.c_int), ("nkf", C.c_int), ("edge_ofs", C.c_int), ("nedge", C.c_int), ("pt_ofs", C.c_int),
+                ("npt", C.c_int), ("iters_done", C.c_int), ("n_trials", C.c_int), ("chi2_before", C.c_double),
+                ("chi2_after", C.c_double)]
 
 
 class BmParams(C.Structure):
@@ -278,7 +286,7 @@ class Context:
 
     def timing_get(self, family):
         ms, n, u = C.c_double(), C.c_longlong(), C.c_longlong()
-        fam = next(t[family] for t in (FAMILIES, KERNEL_FAMILIES, DENSE_FAMILIES, CLOUD_FAMILIES, DEBUG_FAMILIES) if family in t)
+        fam = next(t[family] for t in (FAMILIES, KERNEL_FAMILIES, DENSE_FAMILIES, CLOUD_FAMILIES, LOOP_FAMILIES, DEBUG_FAMILIES) if family in t)
         self._chk(self.L.svslam_timing_get(self.h, fam, C.byref(ms), C.byref(n), C.byref(u)), "timing")
         return ms.value, n.value, u.value
 
@@ -528,6 +536,46 @@ class Context:
             out.append((P[j.kf_ofs:j.kf_ofs + j.nkf].copy(), X[j.lm_ofs:j.lm_ofs + j.nlm].copy(),
                         chi2[j.obs_ofs:j.obs_ofs + j.nobs].copy(), j.iters_done))
         return out
+
+    # ---- global pose-graph optimisation ----------------------------------------
+    def pose_graph(self, jobs, iters=22):
+        """LoopClosure::PoseGraphOptimization for every job in one call (svslam_pose_graph_batch).
+        jobs: list of dicts with poses[n,7], fixed[n], edges = (a, b, meas[e,7]) or None, and optionally pts[m,3] with
+        anchor[m] (vertex a point keeps its coordinates relative to, or -1).
+        returns a list of dicts: poses, pts, iters, trials, chi2_before, chi2_after."""
+        n = len(jobs)
+        arr = (PgJob * n)()
+        P, F, A, B, M, X, AN = [], [], [], [], [], [], []
+        ko = eo = po = 0
+        for i, job in enumerate(jobs):
+            poses = np.ascontiguousarray(job["poses"], np.float64).reshape(-1, 7)
+            fixed = np.ascontiguousarray(job["fixed"], np.uint8).reshape(-1)
+            if len(fixed) != len(poses):
+                raise ValueError("pose_graph: job %d has %d poses and %d fixed flags" % (i, len(poses), len(fixed)))
+            edges = job.get("edges")
+            if edges is None:
+                ea = eb = np.zeros(0, np.int32); meas = np.zeros((0, 7))
+            else:
+                ea = np.ascontiguousarray(edges[0], np.int32).reshape(-1); eb = np.ascontiguousarray(edges[1], np.int32).reshape(-1)
+                meas = np.ascontiguousarray(edges[2], np.float64).reshape(-1, 7)
+                if not (len(ea) == len(eb) == len(meas)):
+                    raise ValueError("pose_graph: job %d: edge arrays of different lengths" % i)
+            pts = job.get("pts")
+            pts = np.zeros((0, 3)) if pts is None else np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+            anchor = job.get("anchor")
+            anchor = np.zeros(0, np.int32) if anchor is None else np.ascontiguousarray(anchor, np.int32).reshape(-1)
+            if len(anchor) != len(pts):
+                raise ValueError("pose_graph: job %d has %d points and %d anchors" % (i, len(pts), len(anchor)))
+            arr[i] = PgJob(ko, len(poses), eo, len(ea), po, len(pts), 0, 0, 0.0, 0.0)
+            ko += len(poses); eo += len(ea); po += len(pts)
+            P.append(poses); F.append(fixed); A.append(ea); B.append(eb); M.append(meas); X.append(pts); AN.append(anchor)
+        cat = lambda v, shape, dt: np.ascontiguousarray(np.concatenate(v)) if v else np.zeros(shape, dt)
+        P = cat(P, (0, 7), np.float64); F = cat(F, 0, np.uint8); A = cat(A, 0, np.int32); B = cat(B, 0, np.int32)
+        M = cat(M, (0, 7), np.float64); X = cat(X, (0, 3), np.float64); AN = cat(AN, 0, np.int32)
+        self._chk(self.L.svslam_pose_graph_batch(self.h, n, arr, ko, _p(P), _p(F), eo, _p(A), _p(B), _p(M), po, _p(AN), _p(X),
+                                                 int(iters)), "pose_graph")
+        return [dict(poses=P[j.kf_ofs:j.kf_ofs + j.nkf].copy(), pts=X[j.pt_ofs:j.pt_ofs + j.npt].copy(), iters=j.iters_done,
+                     trials=j.n_trials, chi2_before=j.chi2_before, chi2_after=j.chi2_after) for j in arr]
 
     # ---- shared-map BA (one rank's shard; the LM driver is shared_ba.py) ---------
     def sba_open(self, cam_l, ext_l, cam_r, ext_r, poses, pts, okf, olm, ori, ouv, huber_delta=5.991):

@@ -45,6 +45,7 @@ typedef enum { ncclDouble = 8 } ncclDataType_t;
 #include "k_dmap.h"
 #include "k_stereo_bm.h"
 #include "k_cloud_filter.h"
+#include "k_pose_graph.h"
 
 #define SVSLAM_DMAP_CHUNK 512     /* keyframe jobs per svslam_dmap_keyframe_batch call the staging arena is sized for */
 #define SVSLAM_DMAP_EVICT_PER_JOB 512   /* evicted-landmark records per job of a call (shared by the call's jobs; the surplus waits) */
@@ -57,6 +58,7 @@ enum { FAM_PYR = 0, FAM_LK, FAM_GFTT, FAM_TRI, FAM_POSE, FAM_BA,
        FAM_DBG0, FAM_DBG1, FAM_DBG2, FAM_DBG3,      // development (SVSLAM_TIMING_SPLIT): 7 .. 10
        FAM_BA_SOLVE,   // 11: the local-BA solver kernel(s) alone, nested inside FAM_BA (gather + build + solve + scatter)
        FAM_CF,         // 12: "cloud_filter", the outlier-removal and voxel-grid kernels with their sorts (units = points); appended, nothing moved
+       FAM_PG,         // 13: "pose_graph", svslam_pose_graph_batch (units = jobs); appended, nothing moved
        FAM_COUNT };
 
 struct Timing {
@@ -104,6 +106,9 @@ struct svslam_ctx {
     struct CfBuf { void *p = nullptr; size_t cap = 0; };
     struct { CfBuf xyz, rgb, segs, keys, keys2, vals, vals2, soa, out, flag, pos, start, oxyz, orgb, tmp; unsigned *climbs = nullptr;
              long long queries = 0, climbed = 0; } cf;
+    // pose graph (svslam_pose_graph_batch): one device buffer (inputs, results, solver scratch) and its pageable host mirror of the
+    // uploaded part, sized at first use, grown on demand and kept
+    struct { unsigned char *d = nullptr; size_t cap = 0; std::vector<unsigned char> h; PgPlan plan; } pg;
     // BA scratch
     BaWork bw;
     int bw_jobs = 0;          // problems per call the BA scratch holds
@@ -777,6 +782,7 @@ void svslam_destroy(svslam_ctx *c)
     for (svslam_ctx::CfBuf *b : { &c->cf.xyz, &c->cf.rgb, &c->cf.segs, &c->cf.keys, &c->cf.keys2, &c->cf.vals, &c->cf.vals2, &c->cf.soa, &c->cf.out,
                                   &c->cf.flag, &c->cf.pos, &c->cf.start, &c->cf.oxyz, &c->cf.orgb, &c->cf.tmp }) (void)hipFree(b->p);
     (void)hipFree(c->cf.climbs);
+    (void)hipFree(c->pg.d);
     ba_work_free(c->bw);
     ll_release(c);
     if (c->d_ba_prof) (void)hipFree(c->d_ba_prof);
@@ -2590,6 +2596,68 @@ int svslam_ba_profile(svslam_ctx *c, int enable, long long *out12)
         HIPCHK(c, hipMemset(c->d_ba_prof, 0, sizeof(long long) * (BA_PROF_N + 4)));
     }
     if (!enable && c->d_ba_prof) { (void)hipFree(c->d_ba_prof); c->d_ba_prof = nullptr; }
+    return 0;
+}
+
+// ------------------------------------------------------------------ global pose-graph optimisation
+int svslam_pose_graph_batch(svslam_ctx *c, int njobs, svslam_pg_job *jobs, int total_kf, double *poses, const uint8_t *fixed,
+                            int total_edges, const int *edge_a, const int *edge_b, const double *edge_meas,
+                            int total_pts, const int *pt_anchor, double *pts, int iters)
+{
+    if (!c) return -1;
+    if (njobs < 0 || total_kf < 0 || total_edges < 0 || total_pts < 0) return fail(c, "pose_graph: negative count");
+    if (iters < 0) return fail(c, "pose_graph: iters %d < 0", iters);
+    if (njobs == 0) return 0;
+    if (!jobs) return fail(c, "pose_graph: null jobs");
+    if ((total_kf && (!poses || !fixed)) || (total_edges && (!edge_a || !edge_b || !edge_meas)) || (total_pts && (!pt_anchor || !pts)))
+        return fail(c, "pose_graph: null array");
+    if (arena_busy(c)) return -1;
+    std::vector<PgIn> in((size_t)njobs);
+    for (int j = 0; j < njobs; ++j) {
+        const svslam_pg_job &s = jobs[j];
+        in[(size_t)j] = PgIn{ s.kf_ofs, s.nkf, s.edge_ofs, s.nedge, s.pt_ofs, s.npt };
+    }
+    for (int e = 0; e < total_edges; ++e) {
+        const double *q = edge_meas + 7 * (size_t)e;
+        const double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+        if (!(fabs(n2 - 1.0) <= 2e-6)) return fail(c, "pose_graph: the quaternion of measurement %d is not of unit length (1e-6)", e);
+    }
+    static_assert(LM_TRACE_REC == 6 && LM_TRACE_CAP == 408 && LM_TRACE_STRIDE == 8 + 6 * 408,
+                  "k_pose_graph.h (host emulation) and tests/pose_graph_cases.py restate the trace layout of dev_common.h");
+    PgPlan &P = c->pg.plan;
+    const char *why = pg_plan(njobs, in.data(), total_kf, poses, fixed, total_edges, edge_a, edge_b, total_pts, pt_anchor, iters,
+                              c->d_lm_trace ? c->lim.max_jobs : 0, P);
+    if (why) return fail(c, "pose_graph: %s", why);
+    (void)pg_layout(P, njobs, total_kf, total_edges, total_pts, nullptr);         // sizes
+    if (P.bytes > c->pg.cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(c->pg.d); c->pg.d = nullptr; c->pg.cap = 0;
+        const size_t want = P.bytes + P.bytes / 4;
+        if (hipMalloc(&c->pg.d, want) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, "pose_graph: no device memory for %zu bytes of solver scratch", want);
+        }
+        c->pg.cap = want;
+    }
+    try { if (c->pg.h.size() < P.front_bytes) c->pg.h.resize(P.front_bytes); }
+    catch (const std::bad_alloc &) { return fail(c, "pose_graph: no host memory for %zu bytes of staging", P.front_bytes); }
+    const PgBuf Hb = pg_layout(P, njobs, total_kf, total_edges, total_pts, c->pg.h.data());
+    const PgBuf Db = pg_layout(P, njobs, total_kf, total_edges, total_pts, c->pg.d);
+    pg_fill_front(P, Hb, njobs, total_kf, poses, total_edges, edge_a, edge_b, edge_meas, total_pts, pt_anchor, pts);
+    HIPCHK(c, hipMemcpyAsync(c->pg.d, c->pg.h.data(), P.front_bytes, hipMemcpyHostToDevice, c->stream));
+    if (c->d_lm_trace) HIPCHK(c, hipMemsetAsync(c->d_lm_trace, 0, sizeof(double) * LM_TRACE_STRIDE * (size_t)std::min(njobs, c->lim.max_jobs), c->stream));
+    tm_begin(c, FAM_PG, njobs);
+    hipLaunchKernelGGL(k_pose_graph, dim3(njobs), dim3(PG_THREADS), 0, c->stream, Db, c->d_lm_trace);
+    tm_end(c);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->pg.h.data(), c->pg.d, P.result_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (d2h_sync(c, 0, 0)) return -1;
+    for (int j = 0; j < njobs; ++j) {
+        const PgJob &J = Hb.jobs[j];
+        jobs[j].iters_done = J.iters_done; jobs[j].n_trials = J.n_trials; jobs[j].chi2_before = J.chi2_before; jobs[j].chi2_after = J.chi2_after;
+    }
+    if (total_kf) memcpy(poses, Hb.poses, 56 * (size_t)total_kf);
+    if (total_pts) memcpy(pts, Hb.pts, 24 * (size_t)total_pts);
     return 0;
 }
 

@@ -111,6 +111,10 @@ public:
                  int iters, double *chi2)
     { return svslam_local_ba_batch(ctx_, n, jobs, cam_l, ext_l, cam_r, ext_r, total_kf, poses, total_lm, pts, total_obs, okf, olm, oright, ouv, delta, iters, chi2); }
 
+    int pose_graph(int n, svslam_pg_job *jobs, int total_kf, double *poses, const uint8_t *fixed, int total_edges, const int *ea,
+                   const int *eb, const double *meas, int total_pts, const int *anchor, double *pts, int iters)
+    { return svslam_pose_graph_batch(ctx_, n, jobs, total_kf, poses, fixed, total_edges, ea, eb, meas, total_pts, anchor, pts, iters); }
+
     int local_ba_submit(int n, const svslam_ba_job *jobs, const double *cam_l, const double *ext_l, const double *cam_r,
                         const double *ext_r, int total_kf, const double *poses, int total_lm, const double *pts,
                         int total_obs, const int *okf, const int *olm, const uint8_t *oright, const float *ouv,

@@ -70,6 +70,14 @@ int svs_pipe_run_device(void *p, const void *left_base, const void *right_base, 
 int svs_pipe_counters_get(void *p, svs_pipe_counters *out);
 /* keyframes.txt + landmarks.pcd of one stream, in the reference's formats (src/visual_odometry.cpp:198-310) */
 int svs_pipe_save_outputs(void *p, int stream, const char *dir, const char *dataset_dir, int left_cam_index);
+/* Frame::loop_keyframe_ / loop_relative_pose_ of keyframe kf_id (src/loopclosure.cpp:598-606): T_rel7 = T_kf * T_loop^-1 as a loop
+ * detector measured it.  -1 (svs_pipe_last_error): ids that are not keyframes of the stream, loop_kf_id >= kf_id. */
+int svs_pipe_add_loop_edge(void *p, int stream, long long kf_id, long long loop_kf_id, const double *T_rel7);
+/* LoopClosure::PoseGraphOptimization (src/loopclosure.cpp:641-799) for `nstreams` streams (streams == NULL: all) in one kernel call:
+ * keyframe poses and every landmark svs_pipe_save_outputs writes are corrected, relative_pose_pkf refreshed.  stats7_or_null: per
+ * stream nkf, nedge, npt, iterations, trials, chi2 before, chi2 after.  -1: the map lives on the device (device_map = 1: nothing
+ * is done), a bad stream, the kernel's refusal.  Product library only. */
+int svs_pipe_pose_graph_optimization(void *p, int nstreams, const int *streams, int iters, double *stats7_or_null);
 /* Inspection hook (host map only): the map of one stream as it stands after the last step, flat.
  *   ints: n_active_keyframes, (keyframe id)*, n_active_landmarks, per landmark { id, observed_times, n_obs,
  *         (keyframe id, 0 left / 1 right, index of the feature in that keyframe's list)* }  — ids ascending, observations in list order

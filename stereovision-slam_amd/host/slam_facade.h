@@ -338,6 +338,12 @@ public:
         return true;
     }
     Pipeline<K> *pipeline() { return pipe_.get(); }
+    // what the reference's LoopClosure leaves on a keyframe after a confirmed loop (src/loopclosure.cpp:598-606), for a caller that
+    // brings its own place recognition: keyframe kf_id saw the older keyframe loop_kf_id again, T_rel = T_kf * T_loop^-1 as measured
+    bool AddLoopEdge(unsigned long kf_id, unsigned long loop_kf_id, const SE3 &T_rel)
+    {
+        return pipe_ && pipe_->AddLoopEdge(0, (long)kf_id, (long)loop_kf_id, T_rel);
+    }
     K *kernels() { return kernels_.get(); }
     bool LowLatency() const { return opt_.low_latency != 0; }
 
@@ -515,8 +521,19 @@ public:
     {
         while (step()) {}
         if (backend_) backend_->Stop();
+        if (!Stop())        // refused (the map lives on the device): say so, the outputs below are the uncorrected ones
+            std::fprintf(stderr, "VisualOdometry: global pose-graph optimisation not run: %s\n", frontend_->pipeline()->last_error().c_str());
         saveSLAMOutputInFile();
     }
+    // LoopClosure::Stop() (src/visual_odometry.cpp:174-190, src/loopclosure.cpp:66-82): with global_pose_graph_optimization >= 1 one
+    // pose-graph optimisation over the whole run before the outputs are written.  False: the optimisation was refused
+    // (device-resident map); the outputs are then written uncorrected.
+    bool Stop()
+    {
+        if ((int)config_.Num("global_pose_graph_optimization", 0) < 1 || !frontend_->pipeline()) return true;
+        return frontend_->pipeline()->PoseGraphOptimization({ 0 });
+    }
+    bool AddLoopEdge(unsigned long kf_id, unsigned long loop_kf_id, const SE3 &T_rel) { return frontend_->AddLoopEdge(kf_id, loop_kf_id, T_rel); }
     FrontendStatus GetFrontendStatus() const { return frontend_->GetStatus(); }
     // keyframes.txt + landmarks.pcd under output_dir (:198-310; the reference adds a time-stamped folder)
     bool saveSLAMOutputInFile(const std::string &dir_override = "")

@@ -101,6 +101,9 @@ def _bind(L):
     L.svs_pipe_backend_ctx.argtypes = [C.c_void_p]
     L.svs_pipe_kernel_ctx.restype = C.c_void_p
     L.svs_pipe_kernel_ctx.argtypes = [C.c_void_p]
+    if hasattr(L, "svs_pipe_add_loop_edge"):        # product library only (the CPU twins have no pose-graph provider)
+        L.svs_pipe_add_loop_edge.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p]
+        L.svs_pipe_pose_graph_optimization.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     return L
 
 
@@ -184,6 +187,23 @@ class Pipeline:
         rc = self.L.svs_pipe_save_outputs(self.h, stream, out_dir.encode(), dataset_dir.encode(), left_cam_index)
         if rc != 0:
             raise RuntimeError("svs_pipe_save_outputs failed (%d)" % rc)
+
+    def add_loop_edge(self, stream, kf_id, loop_kf_id, T_rel):
+        """records that keyframe kf_id closes a loop with the older keyframe loop_kf_id; T_rel = T_kf * T_loop^-1 (double[7])"""
+        T = np.ascontiguousarray(T_rel, np.float64).reshape(7)
+        if self.L.svs_pipe_add_loop_edge(self.h, stream, C.c_longlong(kf_id), C.c_longlong(loop_kf_id), T.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("svs_pipe_add_loop_edge refused: " + self.L.svs_pipe_last_error().decode())
+
+    def pose_graph_optimization(self, streams=None, iters=22):
+        """LoopClosure::PoseGraphOptimization for the given streams (default: all) in one kernel call; returns one dict per stream
+        (nkf, nedge, npt, iters, trials, chi2_before, chi2_after)"""
+        ss = list(range(self.n)) if streams is None else list(streams)
+        arr = (C.c_int * max(len(ss), 1))(*ss)
+        st = np.zeros((max(len(ss), 1), 7))
+        if self.L.svs_pipe_pose_graph_optimization(self.h, len(ss), arr, int(iters), st.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("svs_pipe_pose_graph_optimization failed: " + self.L.svs_pipe_last_error().decode())
+        keys = ("nkf", "nedge", "npt", "iters", "trials")
+        return [dict({k: int(r[i]) for i, k in enumerate(keys)}, chi2_before=float(r[5]), chi2_after=float(r[6])) for r in st[:len(ss)]]
 
     def map_snapshot(self, stream=0):
         """the host map of one stream after the last step (svs_pipe_map_snapshot): active keyframe ids and poses, active landmarks

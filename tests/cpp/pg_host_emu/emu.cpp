@@ -1,0 +1,42 @@
+// csrc/k_pose_graph.h compiled for the host (tests/test_host_emulation_pose_graph.py): with PG_HOST_EMU the HIP qualifiers vanish and a
+// phase of the one-wave kernel becomes a loop over its 64 lane numbers (the phases end at the kernel's barriers and no lane reads
+// what another lane writes inside a phase, so running the lanes one after the other is the same computation).  The plan, the buffer
+// layout and the solver are the library's own code; only the launch and the copies are restated here.
+#define PG_HOST_EMU
+#include "../../../stereovision-slam_amd/csrc/k_pose_graph.h"
+#include <string>
+
+struct EmuJob { int kf_ofs, nkf, edge_ofs, nedge, pt_ofs, npt, iters_done, n_trials; double chi2_before, chi2_after; };
+static std::string g_err;
+
+extern "C" const char *emu_pg_error() { return g_err.c_str(); }
+
+// trace_or_null: [njobs][LM_TRACE_STRIDE] doubles as svslam_lm_trace keeps them
+extern "C" int emu_pose_graph(int njobs, EmuJob *jobs, int total_kf, double *poses, const uint8_t *fixed, int total_edges, const int *ea,
+                              const int *eb, const double *meas, int total_pts, const int *anchor, double *pts, int iters, double *trace_or_null)
+{
+    std::vector<PgIn> in((size_t)njobs);
+    for (int j = 0; j < njobs; ++j) in[(size_t)j] = PgIn{ jobs[j].kf_ofs, jobs[j].nkf, jobs[j].edge_ofs, jobs[j].nedge, jobs[j].pt_ofs, jobs[j].npt };
+    for (int e = 0; e < total_edges; ++e) {
+        const double *q = meas + 7 * (size_t)e;
+        if (!(fabs(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] - 1.0) <= 2e-6)) { g_err = "measurement quaternion"; return -1; }
+    }
+    PgPlan P;
+    const char *why = pg_plan(njobs, in.data(), total_kf, poses, fixed, total_edges, ea, eb, total_pts, anchor, iters, trace_or_null ? njobs : 0, P);
+    if (why) { g_err = why; return -1; }
+    (void)pg_layout(P, njobs, total_kf, total_edges, total_pts, nullptr);
+    std::vector<double> mem(P.bytes / 8 + 1);
+    const PgBuf B = pg_layout(P, njobs, total_kf, total_edges, total_pts, (unsigned char *)mem.data());
+    pg_fill_front(P, B, njobs, total_kf, poses, total_edges, ea, eb, meas, total_pts, anchor, pts);
+    if (trace_or_null) memset(trace_or_null, 0, sizeof(double) * LM_TRACE_STRIDE * (size_t)njobs);
+    for (int j = 0; j < njobs; ++j) {
+        PgShared S;
+        memset(&S, 0, sizeof(S));
+        pg_run(B, B.jobs[j], S, trace_or_null);
+        jobs[j].iters_done = B.jobs[j].iters_done; jobs[j].n_trials = B.jobs[j].n_trials;
+        jobs[j].chi2_before = B.jobs[j].chi2_before; jobs[j].chi2_after = B.jobs[j].chi2_after;
+    }
+    if (total_kf) memcpy(poses, B.poses, 56 * (size_t)total_kf);
+    if (total_pts) memcpy(pts, B.pts, 24 * (size_t)total_pts);
+    return 0;
+}
