@@ -351,6 +351,56 @@ int svslam_pose_graph_batch(svslam_ctx *ctx, int njobs, svslam_pg_job *jobs,
                             int total_pts, const int *pt_anchor /* local vertex or -1 */, double *pts /* in/out */,
                             int iters);
 
+/* ---- loop verification: Hamming match, PnP RANSAC, loop gates ---------------------
+ * Replaces LoopClosure::KeypointMatchWithLoopCandid and LoopClosure::CalculatePose (src/loopclosure.cpp:286-437, called at :831-862).
+ * One job is one keyframe pair of one stream: nc descriptors of the candidate (older) keyframe with the landmark of each one's
+ * feature (has_xyz = 0 where the reference's map_point_.lock() fails), nq descriptors of the current keyframe with each one's pixel.
+ * Match (:291-326): BruteForce-Hamming match(query = candidate, train = current) — every candidate row takes the nearest current
+ * row over 256 bits, the lowest current index on a tie, no cross-check; thr = max(2 d_min, 30); matches with distance <= thr are
+ * kept in ascending (candidate row, current row); fewer than min_matches: SVSLAM_LOOP_FEW_MATCHES (also nc == 0 or nq == 0, where
+ * the reference dereferences min_element of an empty vector).  3-D filter (:340-371): matches without a landmark are dropped,
+ * landmarks rounded to float (cv::Point3f); fewer than max(min_matches, 4): FEW_POINTS.  PnP RANSAC (:375-398) is this library's own
+ * procedure: ransac_iters hypotheses, hypothesis i draws 4 distinct point indices from a stateless hash of (seed, i,
+ * draw), P3P on the first three, the fourth chooses among the solutions, a degenerate sample gives no hypothesis; inlier: depth > 0
+ * and squared reprojection error <= reproj_px^2; the winner has the most inliers (lowest i on a tie), all hypotheses are evaluated;
+ * fewer than min_matches inliers or no hypothesis: FEW_INLIERS.  The inliers reported are the winner's, before the refinement: LM on
+ * exp(d) T over them, squared pixel error, no robust kernel, g2o's control as svslam_local_ba_batch has it, 10 iterations.
+ * Declared deviations from cv::solvePnPRansac: EPnP on 5 points there, cv::RNG, an early stop at confidence 0.99, no depth test,
+ * solvePnP(ITERATIVE) from a DLT start as the refinement.  Gates (:400-436): T_corr = ext_l^-1 T_pnp, T_rel = T_corr T_cand^-1;
+ * |log T_rel| > max_pose_distance: TOO_FAR; d = |log(T_cur T_corr^-1)| > max_pose_difference: TOO_DIFFERENT; else ACCEPTED with
+ * need_correction = d > min_pose_difference (log: Sophus' 6-vector).
+ * Every output is defined for every status: counts 0, poses the identity, d 0 where a stage was not reached.  A job's match list
+ * (candidate row, current row, distance, inlier flag; rows local to the job) starts at its c_ofs in the four match arrays and has
+ * n_matches entries; what lies behind them in the job's range is not specified.
+ * Errors, nothing written: nc or nq above 1024; a pose or ext_l quaternion whose squared norm is further than 2e-6 from 1; jobs
+ * whose c / q ranges do not ascend from job to job or overlap (gaps are allowed) or leave the arrays; ransac_iters outside
+ * [1, 1024]; a negative min_matches or reproj_px; no memory for the call's buffer (allocated inside the call on demand and kept;
+ * svslam_limits has no say in it, njobs is not bounded by max_jobs).  Valid no-ops: njobs == 0; a job with nc == 0 or nq == 0.
+ * A job's result does not depend on the other jobs of the call, and two calls on the same inputs give the same bits.   */
+enum { SVSLAM_LOOP_ACCEPTED = 0, SVSLAM_LOOP_FEW_MATCHES = 1, SVSLAM_LOOP_FEW_POINTS = 2, SVSLAM_LOOP_FEW_INLIERS = 3,
+       SVSLAM_LOOP_TOO_FAR = 4, SVSLAM_LOOP_TOO_DIFFERENT = 5 };
+typedef struct svslam_loop_job {
+    int c_ofs, nc;          /* candidate rows: desc_c, xyz_c, has_xyz; the job's match list starts at c_ofs too */
+    int q_ofs, nq;          /* current rows: desc_q, uv_q */
+    double T_cur[7], T_cand[7];      /* Frame::Pose() of the two keyframes */
+    int status;             /* out: SVSLAM_LOOP_* */
+    int n_matches, n_points, n_inliers, need_correction, reserved;   /* out */
+    double T_corr[7], T_rel[7], d;   /* out */
+} svslam_loop_job;
+typedef struct svslam_loop_params {
+    double cam[4], ext_l[7];         /* the left camera */
+    int min_matches;                 /* min_num_acceptable_keypoint_match */
+    int ransac_iters;                /* 100 */
+    double reproj_px;                /* 5.991, a pixel radius */
+    double max_pose_distance;        /* max_pose_distance_between_loop_keyframes */
+    double min_pose_difference, max_pose_difference;   /* m{in,ax}_pose_differnece_between_old_new */
+    unsigned seed; int reserved;
+} svslam_loop_params;
+int svslam_loop_verify_batch(svslam_ctx *ctx, int njobs, svslam_loop_job *jobs, const svslam_loop_params *params,
+                             int total_c, const uint8_t *desc_c /* 32 each */, const double *xyz_c /* 3 each */, const uint8_t *has_xyz,
+                             int total_q, const uint8_t *desc_q /* 32 each */, const float *uv_q /* 2 each */,
+                             int *match_c, int *match_q, int *match_dist, uint8_t *match_inlier /* out, total_c each */);
+
 /* ---- shared-map bundle adjustment (BASELINE config 5; not in the reference) -----------
  * ONE local-BA problem whose landmarks are sharded over the GPUs of a node: every rank holds all
  * nkf poses and its landmarks with their edges.  The rank opens its shard, then runs the pieces of
@@ -553,7 +603,8 @@ int svslam_sync(svslam_ctx *ctx);
  * Accumulated per kernel family since the last reset; used by bench.py for
  * the roofline entry.  family: 0 pyramid, 1 lk, 2 gftt, 3 triangulate,
  * 4 pose_only, 5 local_ba, 6 stereo_bm (units = jobs), 12 cloud_filter (units = points; appended
- * after the last number in use, nothing moved), 13 pose_graph (units = jobs; appended after 12, nothing moved).
+ * after the last number in use, nothing moved), 13 pose_graph (units = jobs; appended after 12, nothing moved),
+ * 14 loop_verify (units = jobs; appended after 13, nothing moved).
  * Development families follow and are NOT stable numbers: with stereo_bm taking 6, the
  * per-kernel split moved from 6-9 to 7-10 and the local-BA solver interval from 10 to 11.
  * A caller that passed those raw numbers must move with them (Python addresses them by name). */

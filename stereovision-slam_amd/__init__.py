@@ -20,7 +20,7 @@ ABI_SYMBOLS = [
     "svslam_create", "svslam_destroy", "svslam_last_error", "svslam_build_info",
     "svslam_pyramid_batch", "svslam_pyramid_decimate_batch", "svslam_set_source_size", "svslam_set_low_latency", "svslam_set_pose_only_xtol", "svslam_get_pose_only_xtol", "svslam_pyramid_read",
     "svslam_pyramid_read_padded", "svslam_stereo_bm_batch", "svslam_stereo_bm_strip_rows", "svslam_dense_cloud_batch", "svslam_cloud_sor_batch", "svslam_cloud_voxel_grid", "svslam_debug_cloud_sor_climbs", "svslam_lk_batch", "svslam_gftt_batch", "svslam_gftt_eigmap", "svslam_triangulate_batch",
-    "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect", "svslam_pose_graph_batch",
+    "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect", "svslam_pose_graph_batch", "svslam_loop_verify_batch",
     "svslam_track_batch", "svslam_rtrack_batch", "svslam_rtrack_upload",
     "svslam_sba_io_doubles", "svslam_sba_open", "svslam_sba_phase", "svslam_sba_close",
     "svslam_device_count", "svslam_dmap_keyframe_batch", "svslam_dmap_ba_collect", "svslam_dmap_read", "svslam_dmap_evicted", "svslam_sba_comm_unique_id", "svslam_sba_comm_init", "svslam_sba_comm_destroy", "svslam_sba_solve",
@@ -36,13 +36,14 @@ DEBUG_FAMILIES = {"dbg0": 7, "dbg1": 8, "dbg2": 9, "dbg3": 10}     # per-kernel 
 # inside "local_ba" (= map gather + structure build + solver + scatter)
 KERNEL_FAMILIES = {"ba_solve": 11}
 CLOUD_FAMILIES = {"cloud_filter": 12}      # the outlier removal and the voxel grid of the dense program (units = points); appended, nothing renumbered
-LOOP_FAMILIES = {"pose_graph": 13}         # svslam_pose_graph_batch (units = jobs); appended after 12, nothing renumbered
+# svslam_pose_graph_batch, svslam_loop_verify_batch (units = jobs); appended after 12 and after 13, nothing renumbered
+LOOP_FAMILIES = {"pose_graph": 13, "loop_verify": 14}
 # the HIP kernel(s) behind each timing family at the batch operating point (what a rocprofv3 --kernel-trace --stats row is named)
 FAMILY_KERNELS = {"pyramid": ["k_pyr_fused"], "lk": ["k_lk"], "gftt": ["k_gftt_eig3", "k_gftt_select2"], "triangulate": ["k_triangulate"],
                   "pose_only": ["k_pose_only"], "local_ba": ["k_dmap_ba_gather", "k_ba_build", "k_local_ba_t", "k_dmap_ba_scatter"],
                   "ba_solve": ["k_local_ba_t"], "stereo_bm": ["k_bm_fill", "k_stereo_bm", "k_dense_cloud"],
                   "cloud_filter": ["k_cf_keys", "k_cf_gather", "k_cf_knn", "k_vg_keys", "k_vg_heads", "k_vg_starts", "k_vg_reduce"],
-                  "pose_graph": ["k_pose_graph"]}
+                  "pose_graph": ["k_pose_graph"], "loop_verify": ["k_loop_verify"]}
 
 
 class Limits(C.Structure):
@@ -88,6 +89,24 @@ class PgJob(C.Structure):
     _fields_ = [("kf_ofs", C.c_int), ("nkf", C.c_int), ("edge_ofs", C.c_int), ("nedge", C.c_int), ("pt_ofs", C.c_int),
                 ("npt", C.c_int), ("iters_done", C.c_int), ("n_trials", C.c_int), ("chi2_before", C.c_double),
                 ("chi2_after", C.c_double)]
+
+
+class LoopJob(C.Structure):
+    _fields_ = [("c_ofs", C.c_int), ("nc", C.c_int), ("q_ofs", C.c_int), ("nq", C.c_int), ("T_cur", C.c_double * 7),
+                ("T_cand", C.c_double * 7), ("status", C.c_int), ("n_matches", C.c_int), ("n_points", C.c_int), ("n_inliers", C.c_int),
+                ("need_correction", C.c_int), ("reserved", C.c_int), ("T_corr", C.c_double * 7), ("T_rel", C.c_double * 7), ("d", C.c_double)]
+
+
+class LoopParams(C.Structure):
+    _fields_ = [("cam", C.c_double * 4), ("ext_l", C.c_double * 7), ("min_matches", C.c_int), ("ransac_iters", C.c_int),
+                ("reproj_px", C.c_double), ("max_pose_distance", C.c_double), ("min_pose_difference", C.c_double),
+                ("max_pose_difference", C.c_double), ("seed", C.c_uint), ("reserved", C.c_int)]
+
+
+LOOP_STATUS = ("ACCEPTED", "FEW_MATCHES", "FEW_POINTS", "FEW_INLIERS", "TOO_FAR", "TOO_DIFFERENT")
+# the reference's constants (src/loopclosure.cpp:381) and the values of its config for the loop keys
+LOOP_DEFAULTS = dict(min_matches=20, ransac_iters=100, reproj_px=5.991, max_pose_distance=20.0, min_pose_difference=1.0,
+                     max_pose_difference=50.0, seed=0)
 
 
 class BmParams(C.Structure):
@@ -576,6 +595,50 @@ class Context:
                                                  int(iters)), "pose_graph")
         return [dict(poses=P[j.kf_ofs:j.kf_ofs + j.nkf].copy(), pts=X[j.pt_ofs:j.pt_ofs + j.npt].copy(), iters=j.iters_done,
                      trials=j.n_trials, chi2_before=j.chi2_before, chi2_after=j.chi2_after) for j in arr]
+
+    # ---- loop verification -----------------------------------------------------
+    def loop_verify(self, jobs, cam, ext_l, **params):
+        """LoopClosure::KeypointMatchWithLoopCandid + CalculatePose for every job in one call (svslam_loop_verify_batch).
+        jobs: list of dicts with desc_c [nc, 32] u8, desc_q [nq, 32] u8, xyz_c [nc, 3], has_xyz [nc], uv_q [nq, 2], T_cur[7], T_cand[7].
+        params: min_matches, ransac_iters, reproj_px, max_pose_distance, min_pose_difference, max_pose_difference, seed (LOOP_DEFAULTS).
+        returns a list of dicts: status (index into LOOP_STATUS), n_matches, n_points, n_inliers, T_corr, T_rel, d, need_correction,
+        matches [n_matches, 4] = candidate row, current row, Hamming distance, inlier flag."""
+        unknown = set(params) - set(LOOP_DEFAULTS)
+        if unknown:
+            raise TypeError("loop_verify: unknown parameter(s) %s" % sorted(unknown))
+        p = dict(LOOP_DEFAULTS); p.update(params)
+        n = len(jobs)
+        arr = (LoopJob * n)()
+        DC, XC, HX, DQ, UV = [], [], [], [], []
+        co = qo = 0
+        for i, job in enumerate(jobs):
+            dc = np.ascontiguousarray(job["desc_c"], np.uint8).reshape(-1, 32); dq = np.ascontiguousarray(job["desc_q"], np.uint8).reshape(-1, 32)
+            xc = np.ascontiguousarray(job["xyz_c"], np.float64).reshape(-1, 3); hx = np.ascontiguousarray(job["has_xyz"], np.uint8).reshape(-1)
+            uv = _f32(job["uv_q"], 2)
+            if len(xc) != len(dc) or len(hx) != len(dc):
+                raise ValueError("loop_verify: job %d has %d candidate descriptors, %d landmarks and %d flags" % (i, len(dc), len(xc), len(hx)))
+            if len(uv) != len(dq):
+                raise ValueError("loop_verify: job %d has %d current descriptors and %d pixels" % (i, len(dq), len(uv)))
+            arr[i].c_ofs, arr[i].nc, arr[i].q_ofs, arr[i].nq = co, len(dc), qo, len(dq)
+            arr[i].T_cur = (C.c_double * 7)(*_d(job["T_cur"]).reshape(7)); arr[i].T_cand = (C.c_double * 7)(*_d(job["T_cand"]).reshape(7))
+            co += len(dc); qo += len(dq)
+            DC.append(dc); XC.append(xc); HX.append(hx); DQ.append(dq); UV.append(uv)
+        cat = lambda v, shape, dt: np.ascontiguousarray(np.concatenate(v)) if v else np.zeros(shape, dt)
+        DC = cat(DC, (0, 32), np.uint8); XC = cat(XC, (0, 3), np.float64); HX = cat(HX, 0, np.uint8)
+        DQ = cat(DQ, (0, 32), np.uint8); UV = cat(UV, (0, 2), np.float32)
+        P = LoopParams((C.c_double * 4)(*_d(cam).reshape(4)), (C.c_double * 7)(*_d(ext_l).reshape(7)), int(p["min_matches"]),
+                       int(p["ransac_iters"]), float(p["reproj_px"]), float(p["max_pose_distance"]), float(p["min_pose_difference"]),
+                       float(p["max_pose_difference"]), int(p["seed"]) & 0xFFFFFFFF, 0)
+        mc = np.zeros(co, np.int32); mq = np.zeros(co, np.int32); md = np.zeros(co, np.int32); mi = np.zeros(co, np.uint8)
+        self._chk(self.L.svslam_loop_verify_batch(self.h, n, arr, C.byref(P), co, _p(DC), _p(XC), _p(HX), qo, _p(DQ), _p(UV),
+                                                  _p(mc), _p(mq), _p(md), _p(mi)), "loop_verify")
+        out = []
+        for j in arr:
+            s = slice(j.c_ofs, j.c_ofs + j.n_matches)
+            out.append(dict(status=j.status, n_matches=j.n_matches, n_points=j.n_points, n_inliers=j.n_inliers,
+                            need_correction=bool(j.need_correction), T_corr=np.array(j.T_corr), T_rel=np.array(j.T_rel), d=j.d,
+                            matches=np.stack([mc[s], mq[s], md[s], mi[s]], axis=1).astype(np.int64)))
+        return out
 
     # ---- shared-map BA (one rank's shard; the LM driver is shared_ba.py) ---------
     def sba_open(self, cam_l, ext_l, cam_r, ext_r, poses, pts, okf, olm, ori, ouv, huber_delta=5.991):

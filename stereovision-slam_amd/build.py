@@ -4,6 +4,9 @@
   lib/libsvslam_synth.so    CPU generator of the synthetic stereo stream
   lib/libsvslam_pipeline.so C++ host pipeline (Frontend/Backend/Map mirror of the
                             reference) bound to libsvslam_hip.so
+  lib/liblv_host_emu.so     csrc/k_loop_verify.h compiled for the host (tests/cpp/lv_host_emu):
+                            the build fails here, not in a test, when the kernel file stops
+                            being plain C++ between the HIP qualifiers
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the build container.
 """
@@ -97,8 +100,20 @@ def build_pipeline(force=False, verbose=False):
     return out
 
 
+def build_lv_emu(force=False, verbose=False):
+    os.makedirs(LIB, exist_ok=True)
+    out = os.path.join(LIB, "liblv_host_emu.so")
+    main = os.path.join(ROOT, "tests", "cpp", "lv_host_emu", "emu.cpp")
+    if not os.path.exists(main):
+        return None
+    srcs = [main, os.path.join(CSRC, "k_loop_verify.h"), os.path.join(CSRC, "k_pose_graph.h")]
+    if force or _newer(out, srcs):
+        _run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", main, "-o", out], verbose)
+    return out
+
+
 def build_all(force=False, verbose=False):
-    return [build_hip(force, verbose), build_synth(force, verbose), build_pipeline(force, verbose)]
+    return [build_hip(force, verbose), build_synth(force, verbose), build_pipeline(force, verbose), build_lv_emu(force, verbose)]
 
 
 if __name__ == "__main__":

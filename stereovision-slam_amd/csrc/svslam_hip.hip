@@ -46,6 +46,7 @@ typedef enum { ncclDouble = 8 } ncclDataType_t;
 #include "k_stereo_bm.h"
 #include "k_cloud_filter.h"
 #include "k_pose_graph.h"
+#include "k_loop_verify.h"
 
 #define SVSLAM_DMAP_CHUNK 512     /* keyframe jobs per svslam_dmap_keyframe_batch call the staging arena is sized for */
 #define SVSLAM_DMAP_EVICT_PER_JOB 512   /* evicted-landmark records per job of a call (shared by the call's jobs; the surplus waits) */
@@ -59,6 +60,7 @@ enum { FAM_PYR = 0, FAM_LK, FAM_GFTT, FAM_TRI, FAM_POSE, FAM_BA,
        FAM_BA_SOLVE,   // 11: the local-BA solver kernel(s) alone, nested inside FAM_BA (gather + build + solve + scatter)
        FAM_CF,         // 12: "cloud_filter", the outlier-removal and voxel-grid kernels with their sorts (units = points); appended, nothing moved
        FAM_PG,         // 13: "pose_graph", svslam_pose_graph_batch (units = jobs); appended, nothing moved
+       FAM_LV,         // 14: "loop_verify", svslam_loop_verify_batch (units = jobs); appended, nothing moved
        FAM_COUNT };
 
 struct Timing {
@@ -109,6 +111,8 @@ struct svslam_ctx {
     // pose graph (svslam_pose_graph_batch): one device buffer (inputs, results, solver scratch) and its pageable host mirror of the
     // uploaded part, sized at first use, grown on demand and kept
     struct { unsigned char *d = nullptr; size_t cap = 0; std::vector<unsigned char> h; PgPlan plan; } pg;
+    // loop verification (svslam_loop_verify_batch): one device buffer (results, inputs) and its pageable host mirror, grown on demand and kept
+    struct { unsigned char *d = nullptr; size_t cap = 0; std::vector<unsigned char> h; } lv;
     // BA scratch
     BaWork bw;
     int bw_jobs = 0;          // problems per call the BA scratch holds
@@ -783,6 +787,7 @@ void svslam_destroy(svslam_ctx *c)
                                   &c->cf.flag, &c->cf.pos, &c->cf.start, &c->cf.oxyz, &c->cf.orgb, &c->cf.tmp }) (void)hipFree(b->p);
     (void)hipFree(c->cf.climbs);
     (void)hipFree(c->pg.d);
+    (void)hipFree(c->lv.d);
     ba_work_free(c->bw);
     ll_release(c);
     if (c->d_ba_prof) (void)hipFree(c->d_ba_prof);
@@ -2658,6 +2663,66 @@ int svslam_pose_graph_batch(svslam_ctx *c, int njobs, svslam_pg_job *jobs, int t
     }
     if (total_kf) memcpy(poses, Hb.poses, 56 * (size_t)total_kf);
     if (total_pts) memcpy(pts, Hb.pts, 24 * (size_t)total_pts);
+    return 0;
+}
+
+// ------------------------------------------------------------------ loop verification
+int svslam_loop_verify_batch(svslam_ctx *c, int njobs, svslam_loop_job *jobs, const svslam_loop_params *prm, int total_c, const uint8_t *desc_c,
+                             const double *xyz_c, const uint8_t *has_xyz, int total_q, const uint8_t *desc_q, const float *uv_q,
+                             int *match_c, int *match_q, int *match_dist, uint8_t *match_inlier)
+{
+    if (!c) return -1;
+    if (njobs < 0 || total_c < 0 || total_q < 0) return fail(c, "loop_verify: negative count");
+    if (!prm) return fail(c, "loop_verify: null params");
+    if (njobs == 0) return 0;
+    if (!jobs) return fail(c, "loop_verify: null jobs");
+    if ((total_c && (!desc_c || !xyz_c || !has_xyz || !match_c || !match_q || !match_dist || !match_inlier)) || (total_q && (!desc_q || !uv_q)))
+        return fail(c, "loop_verify: null array");
+    if (arena_busy(c)) return -1;
+    std::vector<LvIn> in((size_t)njobs);
+    for (int j = 0; j < njobs; ++j) in[(size_t)j] = LvIn{ jobs[j].c_ofs, jobs[j].nc, jobs[j].q_ofs, jobs[j].nq, jobs[j].T_cur, jobs[j].T_cand };
+    const char *why = lv_check(njobs, in.data(), total_c, total_q, prm->ext_l, prm->ransac_iters, prm->min_matches, prm->reproj_px);
+    if (why) return fail(c, "loop_verify: %s", why);
+    LvParams P;
+    memset(&P, 0, sizeof(P));
+    memcpy(P.cam, prm->cam, sizeof(P.cam)); memcpy(P.ext_l, prm->ext_l, sizeof(P.ext_l));
+    P.reproj2 = prm->reproj_px * prm->reproj_px; P.max_pose_distance = prm->max_pose_distance;
+    P.min_pose_difference = prm->min_pose_difference; P.max_pose_difference = prm->max_pose_difference;
+    P.min_matches = prm->min_matches; P.ransac_iters = prm->ransac_iters; P.seed = prm->seed;
+    LvSizes Z;
+    (void)lv_layout(Z, njobs, total_c, total_q, nullptr);                       // sizes
+    if (Z.bytes > c->lv.cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(c->lv.d); c->lv.d = nullptr; c->lv.cap = 0;
+        const size_t want = Z.bytes + Z.bytes / 4;
+        if (hipMalloc(&c->lv.d, want) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, "loop_verify: no device memory for %zu bytes", want);
+        }
+        c->lv.cap = want;
+    }
+    try { if (c->lv.h.size() < Z.bytes) c->lv.h.resize(Z.bytes); }
+    catch (const std::bad_alloc &) { return fail(c, "loop_verify: no host memory for %zu bytes of staging", Z.bytes); }
+    const LvBuf Hb = lv_layout(Z, njobs, total_c, total_q, c->lv.h.data());
+    const LvBuf Db = lv_layout(Z, njobs, total_c, total_q, c->lv.d);
+    lv_fill(Z, Hb, njobs, in.data(), total_c, desc_c, xyz_c, has_xyz, total_q, desc_q, uv_q);
+    HIPCHK(c, hipMemcpyAsync(c->lv.d, c->lv.h.data(), Z.bytes, hipMemcpyHostToDevice, c->stream));
+    tm_begin(c, FAM_LV, njobs);
+    hipLaunchKernelGGL(k_loop_verify, dim3(njobs), dim3(LV_THREADS), 0, c->stream, Db, P);
+    tm_end(c);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->lv.h.data(), c->lv.d, Z.result_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (d2h_sync(c, 0, 0)) return -1;
+    for (int j = 0; j < njobs; ++j) {
+        const LvJob &J = Hb.jobs[j];
+        jobs[j].status = J.status; jobs[j].n_matches = J.n_matches; jobs[j].n_points = J.n_points; jobs[j].n_inliers = J.n_inliers;
+        jobs[j].need_correction = J.need_correction;
+        memcpy(jobs[j].T_corr, J.T_corr, 56); memcpy(jobs[j].T_rel, J.T_rel, 56); jobs[j].d = J.d;
+    }
+    if (total_c) {
+        memcpy(match_c, Hb.m_c, 4 * (size_t)total_c); memcpy(match_q, Hb.m_q, 4 * (size_t)total_c); memcpy(match_dist, Hb.m_d, 4 * (size_t)total_c);
+        memcpy(match_inlier, Hb.m_inl, (size_t)total_c);
+    }
     return 0;
 }
 

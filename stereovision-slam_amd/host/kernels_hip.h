@@ -115,6 +115,10 @@ public:
                    const int *eb, const double *meas, int total_pts, const int *anchor, double *pts, int iters)
     { return svslam_pose_graph_batch(ctx_, n, jobs, total_kf, poses, fixed, total_edges, ea, eb, meas, total_pts, anchor, pts, iters); }
 
+    int loop_verify(int n, svslam_loop_job *jobs, const svslam_loop_params *prm, int total_c, const uint8_t *desc_c, const double *xyz_c,
+                    const uint8_t *has_xyz, int total_q, const uint8_t *desc_q, const float *uv_q, int *mc, int *mq, int *md, uint8_t *mi)
+    { return svslam_loop_verify_batch(ctx_, n, jobs, prm, total_c, desc_c, xyz_c, has_xyz, total_q, desc_q, uv_q, mc, mq, md, mi); }
+
     int local_ba_submit(int n, const svslam_ba_job *jobs, const double *cam_l, const double *ext_l, const double *cam_r,
                         const double *ext_r, int total_kf, const double *poses, int total_lm, const double *pts,
                         int total_obs, const int *okf, const int *olm, const uint8_t *oright, const float *ouv,

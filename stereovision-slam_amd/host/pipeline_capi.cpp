@@ -37,4 +37,60 @@ extern "C" int svs_pipe_pose_graph_optimization(void *p, int nstreams, const int
         return -1;
     }
 }
+// Loop verification (product build only, like the pose graph)
+extern "C" int svs_pipe_verify_loops(void *p, int nqueries, const svs_loop_query *queries, const void *params, svs_loop_result *results, int *match4_or_null)
+{
+    typedef svs::Pipeline<SVS_PIPE_KERNELS> Pipe;
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    if (nqueries < 0 || (nqueries > 0 && (!queries || !results)) || !params) { g_err = "svs_pipe_verify_loops: null argument"; return -1; }
+    try {
+        std::vector<Pipe::LoopQuery> qs((size_t)nqueries);
+        for (int i = 0; i < nqueries; ++i) {
+            const svs_loop_query &q = queries[i];
+            qs[(size_t)i] = Pipe::LoopQuery{ q.stream, (long)q.kf_id, (long)q.cand_kf_id, q.n_desc_q, q.desc_q, q.n_idx_q, q.feat_q, q.n_desc_c, q.desc_c, q.n_idx_c, q.feat_c };
+        }
+        std::vector<Pipe::LoopResult> rs;
+        if (!h->pipe->VerifyLoops(qs, *static_cast<const svslam_loop_params *>(params), &rs)) { g_err = h->pipe->last_error(); return -1; }
+        size_t row = 0;
+        for (int i = 0; i < nqueries; ++i) {
+            const Pipe::LoopResult &R = rs[(size_t)i];
+            svs_loop_result &o = results[i];
+            o.status = R.status; o.n_matches = R.n_matches; o.n_points = R.n_points; o.n_inliers = R.n_inliers; o.need_correction = R.need_correction ? 1 : 0; o.reserved = 0;
+            std::memcpy(o.T_corr, R.T_corr.v, 56); std::memcpy(o.T_rel, R.T_rel.v, 56); o.d = R.d;
+            if (match4_or_null) {
+                int *m = match4_or_null + 4 * row;
+                std::memset(m, 0, sizeof(int) * 4 * (size_t)queries[i].n_desc_c);
+                for (int k = 0; k < R.n_matches; ++k) { m[4 * k] = R.match_c[(size_t)k]; m[4 * k + 1] = R.match_q[(size_t)k]; m[4 * k + 2] = R.match_dist[(size_t)k]; m[4 * k + 3] = R.match_inlier[(size_t)k]; }
+            }
+            row += (size_t)queries[i].n_desc_c;
+        }
+        return 0;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+extern "C" int svs_pipe_keep_keyframe_features(void *p, int on)
+{
+    static_cast<PipeHandle *>(p)->pipe->SetKeepKeyframeFeatures(on != 0);
+    return 0;
+}
+extern "C" long long svs_pipe_keyframe_features(void *p, int stream, long long kf_id, double *out8, long long cap, double *pose7_or_null)
+{
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    try {
+        std::vector<double> f;
+        double pose[7];
+        if (!h->pipe->KeyframeFeatures(stream, (long)kf_id, &f, pose)) { g_err = h->pipe->last_error(); return -1; }
+        const long long n = (long long)(f.size() / 8);
+        if (out8 && cap >= n) {
+            if (n) std::memcpy(out8, f.data(), sizeof(double) * f.size());
+            if (pose7_or_null) std::memcpy(pose7_or_null, pose, sizeof(pose));
+        }
+        return n;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
 extern "C" void *svs_pipe_backend_ctx(void *p) { return static_cast<PipeHandle *>(p)->kernels->backend_ctx(); }

@@ -78,6 +78,33 @@ int svs_pipe_add_loop_edge(void *p, int stream, long long kf_id, long long loop_
  * stream nkf, nedge, npt, iterations, trials, chi2 before, chi2 after.  -1: the map lives on the device (device_map = 1: nothing
  * is done), a bad stream, the kernel's refusal.  Product library only. */
 int svs_pipe_pose_graph_optimization(void *p, int nstreams, const int *streams, int iters, double *stats7_or_null);
+/* LoopClosure::KeypointMatchWithLoopCandid + CalculatePose (src/loopclosure.cpp:286-437) for nqueries keyframe pairs in one kernel call
+ * (svslam_loop_verify_batch); every ACCEPTED pair is recorded like svs_pipe_add_loop_edge(stream, kf, cand, T_rel).  Per query:
+ * descriptors [n][32] of both keyframes and desc_feat_indx, the reference's map from descriptor row to index in feature_left_.
+ * params: svslam_loop_params (include/svslam.h); its cam and ext_l are replaced by the pipeline's left camera.  results: one
+ * svs_loop_result per query; match4_or_null: 4 ints per candidate descriptor row, query after query (candidate row, current row,
+ * Hamming distance, inlier flag for the first n_matches rows of a query's block).  LocalFusion (:439-582) is not done.
+ * -1 (svs_pipe_last_error, nothing done): the map lives on the device (device_map = 1), an unknown stream, ids that are not
+ * keyframes, cand >= kf, a desc_feat_indx entry out of range or repeated, descriptor count != index count, the kernel's refusal.
+ * Product library only. */
+typedef struct svs_loop_query {
+    int stream; long long kf_id, cand_kf_id;
+    int n_desc_q, n_idx_q; const uint8_t *desc_q; const int *feat_q;
+    int n_desc_c, n_idx_c; const uint8_t *desc_c; const int *feat_c;
+} svs_loop_query;
+typedef struct svs_loop_result {
+    int status, n_matches, n_points, n_inliers, need_correction, reserved;
+    double T_corr[7], T_rel[7], d;
+} svs_loop_result;
+int svs_pipe_verify_loops(void *p, int nqueries, const svs_loop_query *queries, const void *params, svs_loop_result *results, int *match4_or_null);
+/* on != 0: keyframes that leave the window from now on keep their feature lists, as the reference's do (svs_pipe_verify_loops
+ * reads the candidate keyframe's; a keyframe whose lists were released is refused there).  Off by default. */
+int svs_pipe_keep_keyframe_features(void *p, int on);
+/* the left features of keyframe kf_id, read-only: 8 doubles each (x, y, landmark id or -1, outlier flag, has_xyz, X, Y, Z — the
+ * landmark position svs_pipe_verify_loops would gather: the live one, else the archived float one) and, if asked for, the keyframe's
+ * pose.  Returns the number of features (nothing is written when cap is too small: call again), -1 for a bad stream / id or a map
+ * on the device.  svs_pipe_map_snapshot's format is unchanged. */
+long long svs_pipe_keyframe_features(void *p, int stream, long long kf_id, double *out8, long long cap, double *pose7_or_null);
 /* Inspection hook (host map only): the map of one stream as it stands after the last step, flat.
  *   ints: n_active_keyframes, (keyframe id)*, n_active_landmarks, per landmark { id, observed_times, n_obs,
  *         (keyframe id, 0 left / 1 right, index of the feature in that keyframe's list)* }  — ids ascending, observations in list order

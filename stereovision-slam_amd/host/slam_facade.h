@@ -344,6 +344,20 @@ public:
     {
         return pipe_ && pipe_->AddLoopEdge(0, (long)kf_id, (long)loop_kf_id, T_rel);
     }
+    // LoopClosure::KeypointMatchWithLoopCandid + CalculatePose (src/loopclosure.cpp:286-437) for keyframe kf_id against the older
+    // keyframe cand_kf_id, for a caller that brings its own place recognition and 256-bit descriptors: descriptors [n][32] of both
+    // keyframes with desc_feat_indx (descriptor row -> index in feature_left_).  An ACCEPTED result is recorded like AddLoopEdge.
+    // False: refused (pipeline()->last_error()), nothing done.  LocalFusion is the caller's: the result carries what it needs.
+    bool VerifyLoop(unsigned long kf_id, unsigned long cand_kf_id, int nq, const uint8_t *desc_q, const int *feat_q, int nc,
+                    const uint8_t *desc_c, const int *feat_c, const svslam_loop_params &params, typename Pipeline<K>::LoopResult *out)
+    {
+        if (!pipe_) return false;
+        std::vector<typename Pipeline<K>::LoopResult> res;
+        if (!pipe_->VerifyLoops({ typename Pipeline<K>::LoopQuery{ 0, (long)kf_id, (long)cand_kf_id, nq, desc_q, nq, feat_q, nc, desc_c, nc, feat_c } }, params, &res))
+            return false;
+        if (out) *out = res[0];
+        return true;
+    }
     K *kernels() { return kernels_.get(); }
     bool LowLatency() const { return opt_.low_latency != 0; }
 
@@ -534,6 +548,20 @@ public:
         return frontend_->pipeline()->PoseGraphOptimization({ 0 });
     }
     bool AddLoopEdge(unsigned long kf_id, unsigned long loop_kf_id, const SE3 &T_rel) { return frontend_->AddLoopEdge(kf_id, loop_kf_id, T_rel); }
+    // Frontend::VerifyLoop with the thresholds of the configuration file (the keys LoopClosure reads, src/loopclosure.cpp:26-36, in
+    // their spelling) and the reference's constants of solvePnPRansac (:381: 100 iterations, 5.991 px)
+    bool VerifyLoop(unsigned long kf_id, unsigned long cand_kf_id, int nq, const uint8_t *desc_q, const int *feat_q, int nc,
+                    const uint8_t *desc_c, const int *feat_c, typename Pipeline<K>::LoopResult *out, unsigned seed = 0)
+    {
+        svslam_loop_params p;
+        std::memset(&p, 0, sizeof(p));
+        p.min_matches = (int)config_.Num("min_num_acceptable_keypoint_match", 20);
+        p.ransac_iters = 100; p.reproj_px = 5.991; p.seed = seed;
+        p.max_pose_distance = config_.Num("max_pose_distance_between_loop_keyframes", 20);
+        p.min_pose_difference = config_.Num("min_pose_differnece_between_old_new", 1);
+        p.max_pose_difference = config_.Num("max_pose_differnece_between_old_new", 50);
+        return frontend_->VerifyLoop(kf_id, cand_kf_id, nq, desc_q, feat_q, nc, desc_c, feat_c, p, out);
+    }
     FrontendStatus GetFrontendStatus() const { return frontend_->GetStatus(); }
     // keyframes.txt + landmarks.pcd under output_dir (:198-310; the reference adds a time-stamped folder)
     bool saveSLAMOutputInFile(const std::string &dir_override = "")

@@ -31,6 +31,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/svslam.h"
@@ -194,6 +195,9 @@ public:
     size_t num_landmarks() const { return (size_t)next_id_; }                 // Map::landmarks_.size()
     size_t num_resident_landmarks() const { return pool_.size() - free_.size(); }
     void set_keep_archive(bool on) { keep_archive_ = on; }
+    // on: a keyframe keeps its feature lists when it leaves the window, as the reference's do for good (LoopClosure reads
+    // feature_left_ of old keyframes, src/loopclosure.cpp:343-346); off (default): they go back to the allocator
+    void set_keep_features(bool on) { keep_features_ = on; }
     // device-map mode: a landmark the provider freed from its map (K::dmap_evicted) joins the same 20-byte archive (without an anchor)
     void ArchiveEvicted(int id, const float *pos) { if (keep_archive_) archive_.push_back(ArchivedLandmark{ (uint32_t)id, { pos[0], pos[1], pos[2] }, -1 }); }
     size_t num_archived() const { return archive_.size(); }
@@ -255,6 +259,13 @@ public:
     {
         for (const ArchivedLandmark &a : archive_) { for (int k = 0; k < 3; ++k) pts.push_back((double)a.pos[k]); anchor.push_back(a.anchor_kf); }
         for (const MapPoint *m : slots_) if (m) { for (int k = 0; k < 3; ++k) pts.push_back(m->pos[k]); anchor.push_back((int)m->anchor_kf()); }
+    }
+    // id -> archived float position of every dead landmark (Pipeline::VerifyLoops builds it once per call and stream; deque
+    // elements do not move)
+    void ArchiveIndex(std::unordered_map<long, const float *> &idx) const
+    {
+        idx.reserve(archive_.size());
+        for (const ArchivedLandmark &a : archive_) idx[(long)a.id] = a.pos;
     }
     void StoreAnchored(const double *pts)
     {
@@ -318,11 +329,12 @@ public:
     // name are dead: archived and recycled.
     void ReleaseRetired(const std::vector<Feature> *carried = nullptr, long stamp = 0)
     {
-        for (Frame *rm : retired_) {
-            std::vector<Feature>().swap(rm->left);
-            std::vector<Feature>().swap(rm->right);
-            std::vector<uint8_t>().swap(rm->right_ok);
-        }
+        if (!keep_features_)
+            for (Frame *rm : retired_) {
+                std::vector<Feature>().swap(rm->left);
+                std::vector<Feature>().swap(rm->right);
+                std::vector<uint8_t>().swap(rm->right_ok);
+            }
         retired_.clear();
         if (!carried || limbo_.empty()) return;
         for (const Feature &f : *carried)
@@ -358,7 +370,7 @@ private:
     std::vector<MapPoint *> slots_;           // id - base_id_ -> MapPoint (nullptr: evicted)
     long base_id_ = 0, next_id_ = 0;
     std::deque<ArchivedLandmark> archive_;    // (a deque: grows by 512-byte blocks, no doubling reallocation)
-    bool keep_archive_ = true;
+    bool keep_archive_ = true, keep_features_ = false;
     std::vector<Frame *> retired_;            // left the window, feature lists not yet released
     Frame *current_frame_ = nullptr;
     int num_active_keyframes_;
@@ -667,6 +679,133 @@ public:
             m.StoreAnchored(pts.data() + 3 * (size_t)J.pt_ofs);
             if (stats) stats->push_back(PoseGraphStats{ J.nkf, J.nedge, J.npt, J.iters_done, J.n_trials, J.chi2_before, J.chi2_after });
         }
+        return true;
+    }
+    // LoopClosure::KeypointMatchWithLoopCandid + CalculatePose (src/loopclosure.cpp:286-437, as called at :831-862) for every query
+    // in ONE call of the kernel provider.  A query names a keyframe and an older candidate keyframe of one stream and brings the
+    // 256-bit descriptors of both with desc_feat_indx, the reference's map from descriptor row to index in feature_left_.  The
+    // current keyframe's pixels come from kf->left; the candidate's landmarks from Map::point(id), or for a dead landmark from the
+    // stream's archive (a float position: what the reference's cv::Point3f cast keeps anyway); mp == -1 or an id found in neither
+    // place (keep_archive off) is has_xyz = 0, the reference's expired weak_ptr.  Every ACCEPTED result is recorded with
+    // AddLoopEdge(stream, kf, cand, T_rel).  LocalFusion (:439-582) is not done here: the result carries T_corr, need_correction and
+    // the matches (descriptor rows) for it.  A local BA in flight is collected first.  False (last_error(), nothing done):
+    // device_map = 1, an unknown stream, ids that are not keyframes, cand >= kf, a desc_feat_indx entry out of range or repeated,
+    // negative counts or null arrays, the provider's refusal.
+    struct LoopQuery {
+        int stream; long kf_id, cand_kf_id;
+        int nq; const uint8_t *desc_q; int nfq; const int *feat_q;      // current keyframe: descriptors [nq][32], desc_feat_indx [nfq], nfq == nq
+        int nc; const uint8_t *desc_c; int nfc; const int *feat_c;      // candidate keyframe
+    };
+    struct LoopResult {
+        int status = 0, n_matches = 0, n_points = 0, n_inliers = 0; bool need_correction = false;
+        SE3 T_corr, T_rel; double d = 0;
+        std::vector<int> match_c, match_q, match_dist;          // descriptor rows; the features are feat_c[match_c[i]], feat_q[match_q[i]]
+        std::vector<uint8_t> match_inlier;
+    };
+    bool VerifyLoops(const std::vector<LoopQuery> &queries, const svslam_loop_params &params, std::vector<LoopResult> *results)
+    {
+        if (device_map()) return refuse("VerifyLoops: with device_map = 1 the landmarks live on the device without anchors; not supported yet");
+        for (const LoopQuery &q : queries) {
+            if (q.stream < 0 || q.stream >= nstreams()) return refuse("VerifyLoops: no such stream");
+            const std::vector<Frame *> &kfs = streams_[q.stream]->map.keyframes_;
+            if (q.kf_id < 0 || q.kf_id >= (long)kfs.size() || q.cand_kf_id < 0 || q.cand_kf_id >= (long)kfs.size()) return refuse("VerifyLoops: not a keyframe id of this stream");
+            if (q.cand_kf_id >= q.kf_id) return refuse("VerifyLoops: the candidate keyframe must be older than the keyframe");
+            if (q.nq < 0 || q.nc < 0 || q.nq != q.nfq || q.nc != q.nfc) return refuse("VerifyLoops: the descriptor count and the index count differ");
+            if ((q.nq > 0 && (!q.desc_q || !q.feat_q)) || (q.nc > 0 && (!q.desc_c || !q.feat_c))) return refuse("VerifyLoops: null descriptors or desc_feat_indx");
+            for (int side = 0; side < 2; ++side) {
+                const int n = side ? q.nc : q.nq; const int *idx = side ? q.feat_c : q.feat_q;
+                const size_t nf = kfs[(size_t)(side ? q.cand_kf_id : q.kf_id)]->left.size();
+                if (n > 0 && nf == 0) return refuse("VerifyLoops: the keyframe's feature list was released when it left the window (SetKeepKeyframeFeatures)");
+                std::vector<uint8_t> seen(nf, 0);
+                for (int i = 0; i < n; ++i) {
+                    if (idx[i] < 0 || (size_t)idx[i] >= nf) return refuse("VerifyLoops: a desc_feat_indx entry is not a feature of its keyframe");
+                    if (seen[(size_t)idx[i]]) return refuse("VerifyLoops: a desc_feat_indx entry is repeated");
+                    seen[(size_t)idx[i]] = 1;
+                }
+            }
+        }
+        Flush();
+        const int n = (int)queries.size();
+        std::vector<svslam_loop_job> jobs((size_t)n);
+        std::vector<uint8_t> desc_c, desc_q, has;
+        std::vector<double> xyz;
+        std::vector<float> uv;
+        ArchiveCache archive;
+        for (int j = 0; j < n; ++j) {
+            const LoopQuery &q = queries[(size_t)j];
+            Map &m = streams_[q.stream]->map;
+            const Frame *kf = m.keyframes_[(size_t)q.kf_id], *cand = m.keyframes_[(size_t)q.cand_kf_id];
+            svslam_loop_job &J = jobs[(size_t)j];
+            std::memset(&J, 0, sizeof(J));
+            J.c_ofs = (int)has.size(); J.nc = q.nc; J.q_ofs = (int)(uv.size() / 2); J.nq = q.nq;
+            std::memcpy(J.T_cur, kf->pose.v, sizeof(J.T_cur)); std::memcpy(J.T_cand, cand->pose.v, sizeof(J.T_cand));
+            if (q.nq) desc_q.insert(desc_q.end(), q.desc_q, q.desc_q + 32 * (size_t)q.nq);
+            if (q.nc) desc_c.insert(desc_c.end(), q.desc_c, q.desc_c + 32 * (size_t)q.nc);
+            for (int i = 0; i < q.nq; ++i) { const Feature &f = kf->left[(size_t)q.feat_q[i]]; uv.push_back(f.x); uv.push_back(f.y); }
+            for (int i = 0; i < q.nc; ++i) {
+                const long id = cand->left[(size_t)q.feat_c[i]].mp;
+                double p[3] = { 0, 0, 0 };
+                const uint8_t ok = LandmarkPosition(q.stream, id, archive, p) ? 1 : 0;
+                xyz.push_back(p[0]); xyz.push_back(p[1]); xyz.push_back(p[2]); has.push_back(ok);
+            }
+        }
+        svslam_loop_params P = params;
+        std::memcpy(P.cam, cam_l_, sizeof(P.cam)); std::memcpy(P.ext_l, cfg_.cam_l.pose.v, sizeof(P.ext_l));
+        const int tc = (int)has.size(), tq = (int)(uv.size() / 2);
+        std::vector<int> mc((size_t)tc), mq((size_t)tc), md((size_t)tc);
+        std::vector<uint8_t> mi((size_t)tc);
+        if (k_.loop_verify(n, jobs.data(), &P, tc, desc_c.data(), xyz.data(), has.data(), tq, desc_q.data(), uv.data(), mc.data(), mq.data(), md.data(), mi.data()) != 0)
+            return refuse(std::string("VerifyLoops: ") + k_.last_error());
+        if (results) results->clear();
+        for (int j = 0; j < n; ++j) {
+            const svslam_loop_job &J = jobs[(size_t)j];
+            if (J.status == SVSLAM_LOOP_ACCEPTED) AddLoopEdge(queries[(size_t)j].stream, queries[(size_t)j].kf_id, queries[(size_t)j].cand_kf_id, SE3(J.T_rel));
+            if (!results) continue;
+            LoopResult R;
+            R.status = J.status; R.n_matches = J.n_matches; R.n_points = J.n_points; R.n_inliers = J.n_inliers; R.need_correction = J.need_correction != 0;
+            R.T_corr = SE3(J.T_corr); R.T_rel = SE3(J.T_rel); R.d = J.d;
+            R.match_c.assign(mc.begin() + J.c_ofs, mc.begin() + J.c_ofs + J.n_matches); R.match_q.assign(mq.begin() + J.c_ofs, mq.begin() + J.c_ofs + J.n_matches);
+            R.match_dist.assign(md.begin() + J.c_ofs, md.begin() + J.c_ofs + J.n_matches); R.match_inlier.assign(mi.begin() + J.c_ofs, mi.begin() + J.c_ofs + J.n_matches);
+            results->push_back(std::move(R));
+        }
+        return true;
+    }
+    // Keyframes that leave the window from now on keep their feature lists (Map::set_keep_features): VerifyLoops needs the
+    // candidate's.  Off by default: the host store of a long run stays as small as before.
+    void SetKeepKeyframeFeatures(bool on) { for (auto &st : streams_) st->map.set_keep_features(on); }
+    // the position VerifyLoops uses for landmark `id` of stream s: the live landmark's, else the archived float one; false: id == -1
+    // or found in neither place.  The archive's id index of a stream is built when its first dead landmark is asked for.
+    typedef std::unordered_map<int, std::unordered_map<long, const float *>> ArchiveCache;
+    bool LandmarkPosition(int s, long id, ArchiveCache &cache, double *p)
+    {
+        if (id < 0) return false;
+        Map &m = streams_[s]->map;
+        if (const MapPoint *mp = m.point(id)) { p[0] = mp->pos[0]; p[1] = mp->pos[1]; p[2] = mp->pos[2]; return true; }
+        auto it = cache.find(s);
+        if (it == cache.end()) { it = cache.emplace(s, std::unordered_map<long, const float *>()).first; m.ArchiveIndex(it->second); }
+        auto a = it->second.find(id);
+        if (a == it->second.end()) return false;
+        p[0] = a->second[0]; p[1] = a->second[1]; p[2] = a->second[2];
+        return true;
+    }
+    // the left features of a keyframe, read-only: what a descriptor front end samples at, and what VerifyLoops would gather for
+    // them.  8 doubles each: x, y, landmark id or -1, outlier flag, has_xyz, X, Y, Z.  pose7 (optional): the keyframe's pose.
+    bool KeyframeFeatures(int s, long kf_id, std::vector<double> *out8, double *pose7)
+    {
+        if (device_map()) return refuse("KeyframeFeatures: with device_map = 1 the keyframes' features live on the device");
+        if (s < 0 || s >= nstreams()) return refuse("KeyframeFeatures: no such stream");
+        const std::vector<Frame *> &kfs = streams_[s]->map.keyframes_;
+        if (kf_id < 0 || kf_id >= (long)kfs.size()) return refuse("KeyframeFeatures: not a keyframe id of this stream");
+        Flush();
+        ArchiveCache archive;
+        out8->clear();
+        for (const Feature &f : kfs[(size_t)kf_id]->left) {
+            double p[3] = { 0, 0, 0 };
+            const bool ok = LandmarkPosition(s, f.mp, archive, p);
+            const double row[8] = { f.x, f.y, (double)f.mp, f.outlier ? 1.0 : 0.0, ok ? 1.0 : 0.0, p[0], p[1], p[2] };
+            out8->insert(out8->end(), row, row + 8);
+        }
+        if (pose7) std::memcpy(pose7, kfs[(size_t)kf_id]->pose.v, 56);
         return true;
     }
     const std::string &last_error() const { return refusal_; }

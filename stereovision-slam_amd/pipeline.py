@@ -82,6 +82,17 @@ def load_yaml_config(path, **kw):
     return c
 
 
+class LoopQuery(C.Structure):
+    _fields_ = [("stream", C.c_int), ("kf_id", C.c_longlong), ("cand_kf_id", C.c_longlong), ("n_desc_q", C.c_int), ("n_idx_q", C.c_int),
+                ("desc_q", C.c_void_p), ("feat_q", C.c_void_p), ("n_desc_c", C.c_int), ("n_idx_c", C.c_int), ("desc_c", C.c_void_p),
+                ("feat_c", C.c_void_p)]
+
+
+class LoopResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("n_matches", C.c_int), ("n_points", C.c_int), ("n_inliers", C.c_int), ("need_correction", C.c_int),
+                ("reserved", C.c_int), ("T_corr", C.c_double * 7), ("T_rel", C.c_double * 7), ("d", C.c_double)]
+
+
 def _bind(L):
     L.svs_pipe_create.restype = C.c_void_p
     L.svs_pipe_create.argtypes = [C.POINTER(PipeConfig), C.c_int, C.c_int]
@@ -104,6 +115,11 @@ def _bind(L):
     if hasattr(L, "svs_pipe_add_loop_edge"):        # product library only (the CPU twins have no pose-graph provider)
         L.svs_pipe_add_loop_edge.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p]
         L.svs_pipe_pose_graph_optimization.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, "svs_pipe_verify_loops"):
+        L.svs_pipe_verify_loops.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.svs_pipe_keep_keyframe_features.argtypes = [C.c_void_p, C.c_int]
+        L.svs_pipe_keyframe_features.restype = C.c_longlong
+        L.svs_pipe_keyframe_features.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p]
     return L
 
 
@@ -204,6 +220,61 @@ class Pipeline:
             raise RuntimeError("svs_pipe_pose_graph_optimization failed: " + self.L.svs_pipe_last_error().decode())
         keys = ("nkf", "nedge", "npt", "iters", "trials")
         return [dict({k: int(r[i]) for i, k in enumerate(keys)}, chi2_before=float(r[5]), chi2_after=float(r[6])) for r in st[:len(ss)]]
+
+    def keep_keyframe_features(self, on=True):
+        """keyframes that leave the window from now on keep their feature lists (verify_loops reads the candidate keyframe's)"""
+        self.L.svs_pipe_keep_keyframe_features(self.h, 1 if on else 0)
+
+    def keyframe_features(self, stream, kf_id):
+        """the left features of a keyframe, read-only (svs_pipe_keyframe_features): dict(xy [n, 2], mp [n] landmark id or -1,
+        outlier [n], has_xyz [n], xyz [n, 3] — the landmark position verify_loops would gather — and pose[7])"""
+        n = self.L.svs_pipe_keyframe_features(self.h, stream, C.c_longlong(kf_id), None, 0, None)
+        if n < 0:
+            raise RuntimeError("svs_pipe_keyframe_features refused: " + self.L.svs_pipe_last_error().decode())
+        out = np.zeros((max(n, 1), 8)); pose = np.zeros(7)
+        if self.L.svs_pipe_keyframe_features(self.h, stream, C.c_longlong(kf_id), out.ctypes.data_as(C.c_void_p), n, pose.ctypes.data_as(C.c_void_p)) != n:
+            raise RuntimeError("svs_pipe_keyframe_features changed size between two calls")
+        out = out[:n]
+        return dict(xy=out[:, :2].astype(np.float32), mp=out[:, 2].astype(np.int64), outlier=out[:, 3] != 0, has_xyz=out[:, 4] != 0,
+                    xyz=out[:, 5:8].copy(), pose=pose)
+
+    def verify_loops(self, queries, **params):
+        """LoopClosure::KeypointMatchWithLoopCandid + CalculatePose for every query in one kernel call (svs_pipe_verify_loops); every
+        ACCEPTED pair is recorded as a loop edge for pose_graph_optimization.  queries: dicts with stream, kf_id, cand_kf_id, desc_q
+        [nq, 32] u8 and feat_q [nq] (desc_feat_indx) of the keyframe, desc_c / feat_c of the older candidate keyframe.  params: as
+        Context.loop_verify (LOOP_DEFAULTS).  Returns one dict per query: status, n_matches, n_points, n_inliers, need_correction,
+        T_corr, T_rel, d, matches [n_matches, 4] (candidate row, current row, distance, inlier)."""
+        import importlib
+        _svs = importlib.import_module(__package__)          # LOOP_DEFAULTS, LoopParams: the binding of include/svslam.h
+        unknown = set(params) - set(_svs.LOOP_DEFAULTS)
+        if unknown:
+            raise TypeError("verify_loops: unknown parameter(s) %s" % sorted(unknown))
+        p = dict(_svs.LOOP_DEFAULTS); p.update(params)
+        n = len(queries)
+        qs = (LoopQuery * max(n, 1))()
+        keep = []
+        for i, q in enumerate(queries):
+            a = [np.ascontiguousarray(q["desc_q"], np.uint8).reshape(-1, 32), np.ascontiguousarray(q["feat_q"], np.int32).reshape(-1),
+                 np.ascontiguousarray(q["desc_c"], np.uint8).reshape(-1, 32), np.ascontiguousarray(q["feat_c"], np.int32).reshape(-1)]
+            keep.append(a)
+            qs[i] = LoopQuery(int(q["stream"]), int(q["kf_id"]), int(q["cand_kf_id"]), len(a[0]), len(a[1]), a[0].ctypes.data, a[1].ctypes.data,
+                              len(a[2]), len(a[3]), a[2].ctypes.data, a[3].ctypes.data)
+        P = _svs.LoopParams((C.c_double * 4)(), (C.c_double * 7)(), int(p["min_matches"]), int(p["ransac_iters"]), float(p["reproj_px"]),
+                            float(p["max_pose_distance"]), float(p["min_pose_difference"]), float(p["max_pose_difference"]),
+                            int(p["seed"]) & 0xFFFFFFFF, 0)
+        res = (LoopResult * max(n, 1))()
+        rows = sum(len(a[2]) for a in keep)
+        m4 = np.zeros((max(rows, 1), 4), np.int32)
+        if self.L.svs_pipe_verify_loops(self.h, n, qs, C.byref(P), res, m4.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("svs_pipe_verify_loops refused: " + self.L.svs_pipe_last_error().decode())
+        out = []; row = 0
+        for i in range(n):
+            r = res[i]
+            out.append(dict(status=r.status, n_matches=r.n_matches, n_points=r.n_points, n_inliers=r.n_inliers,
+                            need_correction=bool(r.need_correction), T_corr=np.array(r.T_corr), T_rel=np.array(r.T_rel), d=r.d,
+                            matches=m4[row:row + r.n_matches].astype(np.int64)))
+            row += len(keep[i][2])
+        return out
 
     def map_snapshot(self, stream=0):
         """the host map of one stream after the last step (svs_pipe_map_snapshot): active keyframe ids and poses, active landmarks
