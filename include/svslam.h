@@ -401,6 +401,38 @@ int svslam_loop_verify_batch(svslam_ctx *ctx, int njobs, svslam_loop_job *jobs, 
                              int total_q, const uint8_t *desc_q /* 32 each */, const float *uv_q /* 2 each */,
                              int *match_c, int *match_q, int *match_dist, uint8_t *match_inlier /* out, total_c each */);
 
+/* ---- loop-closure descriptors: BRIEF-256 at given points of a keyframe image ----------
+ * Replaces LoopClosure::ExtractKeypointsDescriptor (src/loopclosure.cpp:131-171): cv::ORB::compute at provided keypoints, which carry
+ * cv::KeyPoint's default angle of -1 degree, so no intensity-centroid angle enters; for the integer offsets of a table with |c| <= 13
+ * that rotation rounds back to the table itself: plain BRIEF-256 on a blurred image.  One job is level 0 of one pyramid slot and a
+ * range of points (x, y in xy).  The procedure, every step integer or written-out f32:
+ *   filter   point i is kept iff edge <= x < w - edge and edge <= y < h - edge, compared in float; kept points keep their order; the
+ *            kept rows of a job are the first n_desc rows of its range in desc, desc_pt[row] is the point's index inside the job;
+ *            what lies behind those rows in the caller's arrays is left as it was.  Centre = round-half-to-even of (x, y).
+ *   offsets  once per call: a = cosf(angle_deg (pi / 180)), b = sinf(..) in f32; ix = rint(px a - py b), iy = rint(px b + py a)
+ *            for each of the 512 table points.
+ *   blur     7 taps (18, 34, 49, 54, 49, 34, 18) / 256 = 256 g(sigma 2) rounded, the centre tap absorbing the remainder; separable;
+ *            the horizontal sum is kept in full (<= 65280), the vertical sum over it, out = (v + 32768) >> 16.  Only pixels inside
+ *            the image are read (see the refusals), so no border rule enters.
+ *   tests    bit t (0 .. 255) = B(c + off[2t]) < B(c + off[2t + 1]), strict, on the blurred values; byte t / 8, bit t % 8.
+ * Errors, nothing written: npts > 1024; ranges that do not ascend from job to job, overlap (gaps are allowed) or leave the arrays; a
+ * slot out of range; edge < reach + 4, reach = the largest |ix|, |iy| after the rotation; reach > 24 (the wave's patch in LDS); a table
+ * entry whose two points coincide; an angle that is not finite; no memory for the call's buffer (allocated inside the call on demand
+ * and kept; svslam_limits has no say in it, njobs is not bounded by max_jobs).  Valid no-ops: njobs == 0, npts == 0, an image without
+ * interior (w <= 2 edge).  Non-finite coordinates fail the filter.  A job's result does not depend on the other jobs of the call, and
+ * two calls on the same inputs give the same bits.
+ * The default table (pattern == NULL) is generated by a stateless hash (csrc/k_brief.h says how) and is NOT OpenCV's learned table; a
+ * caller who has that one passes it.  svslam_brief_default_pattern copies the default out. */
+typedef struct svslam_brief_job { int slot; int pt_ofs, npts; int n_desc /* out */; int reserved; } svslam_brief_job;
+typedef struct svslam_brief_params {
+    const int8_t *pattern;   /* [256][4] = x0,y0,x1,y1 per test; NULL: the library's default table */
+    float angle_deg;         /* -1: cv::KeyPoint's default, what the reference's keypoints carry */
+    int   edge;              /* 31: ORB's edgeThreshold */
+} svslam_brief_params;
+int svslam_brief_describe_batch(svslam_ctx *ctx, int njobs, svslam_brief_job *jobs, const svslam_brief_params *params,
+                                int total_pts, const float *xy, uint8_t *desc /* [total_pts][32] */, int *desc_pt /* [total_pts] */);
+int svslam_brief_default_pattern(int8_t out[1024]);
+
 /* ---- shared-map bundle adjustment (BASELINE config 5; not in the reference) -----------
  * ONE local-BA problem whose landmarks are sharded over the GPUs of a node: every rank holds all
  * nkf poses and its landmarks with their edges.  The rank opens its shard, then runs the pieces of
@@ -604,7 +636,7 @@ int svslam_sync(svslam_ctx *ctx);
  * the roofline entry.  family: 0 pyramid, 1 lk, 2 gftt, 3 triangulate,
  * 4 pose_only, 5 local_ba, 6 stereo_bm (units = jobs), 12 cloud_filter (units = points; appended
  * after the last number in use, nothing moved), 13 pose_graph (units = jobs; appended after 12, nothing moved),
- * 14 loop_verify (units = jobs; appended after 13, nothing moved).
+ * 14 loop_verify (units = jobs; appended after 13, nothing moved), 15 brief (units = points; appended after 14, nothing moved).
  * Development families follow and are NOT stable numbers: with stereo_bm taking 6, the
  * per-kernel split moved from 6-9 to 7-10 and the local-BA solver interval from 10 to 11.
  * A caller that passed those raw numbers must move with them (Python addresses them by name). */

@@ -20,7 +20,7 @@ ABI_SYMBOLS = [
     "svslam_create", "svslam_destroy", "svslam_last_error", "svslam_build_info",
     "svslam_pyramid_batch", "svslam_pyramid_decimate_batch", "svslam_set_source_size", "svslam_set_low_latency", "svslam_set_pose_only_xtol", "svslam_get_pose_only_xtol", "svslam_pyramid_read",
     "svslam_pyramid_read_padded", "svslam_stereo_bm_batch", "svslam_stereo_bm_strip_rows", "svslam_dense_cloud_batch", "svslam_cloud_sor_batch", "svslam_cloud_voxel_grid", "svslam_debug_cloud_sor_climbs", "svslam_lk_batch", "svslam_gftt_batch", "svslam_gftt_eigmap", "svslam_triangulate_batch",
-    "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect", "svslam_pose_graph_batch", "svslam_loop_verify_batch",
+    "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect", "svslam_pose_graph_batch", "svslam_loop_verify_batch", "svslam_brief_describe_batch", "svslam_brief_default_pattern",
     "svslam_track_batch", "svslam_rtrack_batch", "svslam_rtrack_upload",
     "svslam_sba_io_doubles", "svslam_sba_open", "svslam_sba_phase", "svslam_sba_close",
     "svslam_device_count", "svslam_dmap_keyframe_batch", "svslam_dmap_ba_collect", "svslam_dmap_read", "svslam_dmap_evicted", "svslam_sba_comm_unique_id", "svslam_sba_comm_init", "svslam_sba_comm_destroy", "svslam_sba_solve",
@@ -36,14 +36,15 @@ DEBUG_FAMILIES = {"dbg0": 7, "dbg1": 8, "dbg2": 9, "dbg3": 10}     # per-kernel 
 # inside "local_ba" (= map gather + structure build + solver + scatter)
 KERNEL_FAMILIES = {"ba_solve": 11}
 CLOUD_FAMILIES = {"cloud_filter": 12}      # the outlier removal and the voxel grid of the dense program (units = points); appended, nothing renumbered
-# svslam_pose_graph_batch, svslam_loop_verify_batch (units = jobs); appended after 12 and after 13, nothing renumbered
-LOOP_FAMILIES = {"pose_graph": 13, "loop_verify": 14}
+# svslam_pose_graph_batch, svslam_loop_verify_batch (units = jobs), svslam_brief_describe_batch (units = points); appended after 12,
+# 13 and 14, nothing renumbered
+LOOP_FAMILIES = {"pose_graph": 13, "loop_verify": 14, "brief": 15}
 # the HIP kernel(s) behind each timing family at the batch operating point (what a rocprofv3 --kernel-trace --stats row is named)
 FAMILY_KERNELS = {"pyramid": ["k_pyr_fused"], "lk": ["k_lk"], "gftt": ["k_gftt_eig3", "k_gftt_select2"], "triangulate": ["k_triangulate"],
                   "pose_only": ["k_pose_only"], "local_ba": ["k_dmap_ba_gather", "k_ba_build", "k_local_ba_t", "k_dmap_ba_scatter"],
                   "ba_solve": ["k_local_ba_t"], "stereo_bm": ["k_bm_fill", "k_stereo_bm", "k_dense_cloud"],
                   "cloud_filter": ["k_cf_keys", "k_cf_gather", "k_cf_knn", "k_vg_keys", "k_vg_heads", "k_vg_starts", "k_vg_reduce"],
-                  "pose_graph": ["k_pose_graph"], "loop_verify": ["k_loop_verify"]}
+                  "pose_graph": ["k_pose_graph"], "loop_verify": ["k_loop_verify"], "brief": ["k_brief_filter", "k_brief_describe"]}
 
 
 class Limits(C.Structure):
@@ -107,6 +108,14 @@ LOOP_STATUS = ("ACCEPTED", "FEW_MATCHES", "FEW_POINTS", "FEW_INLIERS", "TOO_FAR"
 # the reference's constants (src/loopclosure.cpp:381) and the values of its config for the loop keys
 LOOP_DEFAULTS = dict(min_matches=20, ransac_iters=100, reproj_px=5.991, max_pose_distance=20.0, min_pose_difference=1.0,
                      max_pose_difference=50.0, seed=0)
+
+
+class BriefJob(C.Structure):
+    _fields_ = [("slot", C.c_int), ("pt_ofs", C.c_int), ("npts", C.c_int), ("n_desc", C.c_int), ("reserved", C.c_int)]
+
+
+class BriefParams(C.Structure):
+    _fields_ = [("pattern", C.c_void_p), ("angle_deg", C.c_float), ("edge", C.c_int)]
 
 
 class BmParams(C.Structure):
@@ -639,6 +648,43 @@ class Context:
                             need_correction=bool(j.need_correction), T_corr=np.array(j.T_corr), T_rel=np.array(j.T_rel), d=j.d,
                             matches=np.stack([mc[s], mq[s], md[s], mi[s]], axis=1).astype(np.int64)))
         return out
+
+    # ---- loop-closure descriptors ------------------------------------------------
+    def brief_default_pattern(self):
+        """the library's default table of 256 tests, [256, 4] int8 = x0, y0, x1, y1 (svslam_brief_default_pattern)"""
+        out = np.zeros((256, 4), np.int8)
+        if self.L.svslam_brief_default_pattern(_p(out)) != 0:
+            raise RuntimeError("brief_default_pattern failed")
+        return out
+
+    def brief_describe(self, jobs, xy=None, pattern=None, angle_deg=-1.0, edge=31):
+        """BRIEF-256 at points of level 0 of pyramid slots, all jobs in one call (svslam_brief_describe_batch).
+        jobs: list of (slot, xy [n, 2]) with xy=None, or list of (slot, pt_ofs, npts) into the shared array xy [total, 2].
+        pattern: [256, 4] int8 or None for the default table.
+        returns per job (desc [n_desc, 32] u8, desc_pt [n_desc] int32 = index of the row's point inside the job, n_desc)."""
+        n = len(jobs)
+        arr = (BriefJob * n)()
+        if xy is None:
+            parts, o = [], 0
+            for i, (slot, pts) in enumerate(jobs):
+                pts = _f32(pts, 2)
+                arr[i].slot, arr[i].pt_ofs, arr[i].npts = int(slot), o, len(pts)
+                o += len(pts); parts.append(pts)
+            XY = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros((0, 2), np.float32)
+        else:
+            XY = _f32(xy, 2)
+            for i, (slot, ofs, npts) in enumerate(jobs):
+                arr[i].slot, arr[i].pt_ofs, arr[i].npts = int(slot), int(ofs), int(npts)
+        total = len(XY)
+        pat = None
+        if pattern is not None:
+            pat = np.ascontiguousarray(pattern, np.int8)
+            if pat.size != 1024:
+                raise ValueError("brief_describe: the table has %d entries, not 256 x 4" % pat.size)
+        P = BriefParams(pat.ctypes.data if pat is not None else None, float(angle_deg), int(edge))
+        desc = np.zeros((total, 32), np.uint8); dpt = np.zeros(total, np.int32)
+        self._chk(self.L.svslam_brief_describe_batch(self.h, n, arr, C.byref(P), total, _p(XY), _p(desc), _p(dpt)), "brief_describe")
+        return [(desc[j.pt_ofs:j.pt_ofs + j.n_desc].copy(), dpt[j.pt_ofs:j.pt_ofs + j.n_desc].copy(), j.n_desc) for j in arr]
 
     # ---- shared-map BA (one rank's shard; the LM driver is shared_ba.py) ---------
     def sba_open(self, cam_l, ext_l, cam_r, ext_r, poses, pts, okf, olm, ori, ouv, huber_delta=5.991):

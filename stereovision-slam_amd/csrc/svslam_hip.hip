@@ -47,6 +47,7 @@ typedef enum { ncclDouble = 8 } ncclDataType_t;
 #include "k_cloud_filter.h"
 #include "k_pose_graph.h"
 #include "k_loop_verify.h"
+#include "k_brief.h"
 
 #define SVSLAM_DMAP_CHUNK 512     /* keyframe jobs per svslam_dmap_keyframe_batch call the staging arena is sized for */
 #define SVSLAM_DMAP_EVICT_PER_JOB 512   /* evicted-landmark records per job of a call (shared by the call's jobs; the surplus waits) */
@@ -61,6 +62,7 @@ enum { FAM_PYR = 0, FAM_LK, FAM_GFTT, FAM_TRI, FAM_POSE, FAM_BA,
        FAM_CF,         // 12: "cloud_filter", the outlier-removal and voxel-grid kernels with their sorts (units = points); appended, nothing moved
        FAM_PG,         // 13: "pose_graph", svslam_pose_graph_batch (units = jobs); appended, nothing moved
        FAM_LV,         // 14: "loop_verify", svslam_loop_verify_batch (units = jobs); appended, nothing moved
+       FAM_BRIEF,      // 15: "brief", svslam_brief_describe_batch (units = points); appended, nothing moved
        FAM_COUNT };
 
 struct Timing {
@@ -113,6 +115,8 @@ struct svslam_ctx {
     struct { unsigned char *d = nullptr; size_t cap = 0; std::vector<unsigned char> h; PgPlan plan; } pg;
     // loop verification (svslam_loop_verify_batch): one device buffer (results, inputs) and its pageable host mirror, grown on demand and kept
     struct { unsigned char *d = nullptr; size_t cap = 0; std::vector<unsigned char> h; } lv;
+    // descriptors (svslam_brief_describe_batch): the same arrangement
+    struct { unsigned char *d = nullptr; size_t cap = 0; std::vector<unsigned char> h; } br;
     // BA scratch
     BaWork bw;
     int bw_jobs = 0;          // problems per call the BA scratch holds
@@ -788,6 +792,7 @@ void svslam_destroy(svslam_ctx *c)
     (void)hipFree(c->cf.climbs);
     (void)hipFree(c->pg.d);
     (void)hipFree(c->lv.d);
+    (void)hipFree(c->br.d);
     ba_work_free(c->bw);
     ll_release(c);
     if (c->d_ba_prof) (void)hipFree(c->d_ba_prof);
@@ -2723,6 +2728,67 @@ int svslam_loop_verify_batch(svslam_ctx *c, int njobs, svslam_loop_job *jobs, co
         memcpy(match_c, Hb.m_c, 4 * (size_t)total_c); memcpy(match_q, Hb.m_q, 4 * (size_t)total_c); memcpy(match_dist, Hb.m_d, 4 * (size_t)total_c);
         memcpy(match_inlier, Hb.m_inl, (size_t)total_c);
     }
+    return 0;
+}
+
+// ------------------------------------------------------------------ BRIEF descriptors
+int svslam_brief_default_pattern(int8_t *out)
+{
+    if (!out) return -1;
+    memcpy(out, BR_DEFAULT_PATTERN, sizeof(BR_DEFAULT_PATTERN));
+    return 0;
+}
+
+int svslam_brief_describe_batch(svslam_ctx *c, int njobs, svslam_brief_job *jobs, const svslam_brief_params *prm, int total_pts,
+                                const float *xy, uint8_t *desc, int *desc_pt)
+{
+    if (!c) return -1;
+    if (njobs < 0 || total_pts < 0) return fail(c, "brief: negative count");
+    if (!prm) return fail(c, "brief: null params");
+    if (njobs && !jobs) return fail(c, "brief: null jobs");
+    if (total_pts && (!xy || !desc || !desc_pt)) return fail(c, "brief: null array");
+    if (arena_busy(c)) return -1;
+    std::vector<BrJob> in((size_t)njobs);
+    for (int j = 0; j < njobs; ++j) in[(size_t)j] = BrJob{ jobs[j].slot, jobs[j].pt_ofs, jobs[j].npts, 0 };
+    int off[1024], reach = 0;
+    const char *why = br_check(njobs, in.data(), total_pts, c->lim.max_slots, prm->pattern ? prm->pattern : BR_DEFAULT_PATTERN,
+                               prm->angle_deg, prm->edge, off, &reach);
+    if (why) return fail(c, "brief: %s", why);
+    if (njobs == 0) return 0;
+    const PyrGeom &g = c->geom;
+    const BrPlan L = br_plan(reach);
+    BrSizes Z;
+    (void)br_layout(Z, njobs, total_pts, nullptr);                              // sizes
+    if (Z.bytes > c->br.cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(c->br.d); c->br.d = nullptr; c->br.cap = 0;
+        const size_t want = Z.bytes + Z.bytes / 4;
+        if (hipMalloc(&c->br.d, want) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, "brief: no device memory for %zu bytes", want);
+        }
+        c->br.cap = want;
+    }
+    try { if (c->br.h.size() < Z.bytes) c->br.h.resize(Z.bytes); }
+    catch (const std::bad_alloc &) { return fail(c, "brief: no host memory for %zu bytes of staging", Z.bytes); }
+    const BrBuf Hb = br_layout(Z, njobs, total_pts, c->br.h.data());
+    const BrBuf Db = br_layout(Z, njobs, total_pts, c->br.d);
+    br_fill(Hb, L, njobs, in.data(), total_pts, xy, off);
+    BrImg I;
+    I.base = c->d_pyr; I.slot_bytes = g.slot_bytes; I.origin = g.ofs[0] + (size_t)SVS_BORDER * g.pitch[0] + SVS_BORDER;
+    I.pitch = g.pitch[0]; I.w = g.w[0]; I.h = g.h[0];
+    HIPCHK(c, hipMemcpyAsync(c->br.d, c->br.h.data(), Z.upload_bytes, hipMemcpyHostToDevice, c->stream));
+    tm_begin(c, FAM_BRIEF, total_pts);
+    hipLaunchKernelGGL(k_brief_filter, dim3(njobs), dim3(BR_THREADS), 0, c->stream, Db, I, prm->edge, L.R);
+    if (total_pts)
+        hipLaunchKernelGGL(k_brief_describe, dim3((total_pts + BR_ROWS_PER_WG - 1) / BR_ROWS_PER_WG), dim3(BR_THREADS),
+                           (size_t)L.wave_bytes * BR_ROWS_PER_WG, c->stream, Db, I, L, total_pts);
+    tm_end(c);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->br.h.data() + Z.result_ofs, c->br.d + Z.result_ofs, Z.bytes - Z.result_ofs, hipMemcpyDeviceToHost, c->stream));
+    if (d2h_sync(c, 0, 0)) return -1;
+    br_copy_out(Hb, njobs, in.data(), desc, desc_pt);
+    for (int j = 0; j < njobs; ++j) jobs[j].n_desc = in[(size_t)j].n_desc;
     return 0;
 }
 

@@ -119,6 +119,9 @@ public:
                     const uint8_t *has_xyz, int total_q, const uint8_t *desc_q, const float *uv_q, int *mc, int *mq, int *md, uint8_t *mi)
     { return svslam_loop_verify_batch(ctx_, n, jobs, prm, total_c, desc_c, xyz_c, has_xyz, total_q, desc_q, uv_q, mc, mq, md, mi); }
 
+    int brief_describe(int n, svslam_brief_job *jobs, const svslam_brief_params *prm, int total_pts, const float *xy, uint8_t *desc, int *desc_pt)
+    { return svslam_brief_describe_batch(ctx_, n, jobs, prm, total_pts, xy, desc, desc_pt); }
+
     int local_ba_submit(int n, const svslam_ba_job *jobs, const double *cam_l, const double *ext_l, const double *cam_r,
                         const double *ext_r, int total_kf, const double *poses, int total_lm, const double *pts,
                         int total_obs, const int *okf, const int *olm, const uint8_t *oright, const float *ouv,

@@ -93,4 +93,71 @@ extern "C" long long svs_pipe_keyframe_features(void *p, int stream, long long k
         return -1;
     }
 }
+// Loop-closure descriptors (product build only: the CPU twins' providers have no brief_describe)
+extern "C" int svs_pipe_describe_new_keyframes(void *p, const void *brief_params_or_null)
+{
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    try {
+        int n = 0;
+        if (!h->pipe->DescribeNewKeyframes(static_cast<const svslam_brief_params *>(brief_params_or_null), &n)) { g_err = h->pipe->last_error(); return -1; }
+        return n;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+extern "C" long long svs_pipe_keyframe_descriptors(void *p, int stream, long long kf_id, uint8_t *desc32, int *feat, long long cap)
+{
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    try {
+        const std::vector<uint8_t> *d = nullptr;
+        const std::vector<int> *f = nullptr;
+        if (!h->pipe->KeyframeDescriptors(stream, (long)kf_id, &d, &f)) { g_err = h->pipe->last_error(); return -1; }
+        const long long n = (long long)f->size();
+        if (desc32 && feat && cap >= n && n) { std::memcpy(desc32, d->data(), 32 * (size_t)n); std::memcpy(feat, f->data(), sizeof(int) * (size_t)n); }
+        return n;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+extern "C" int svs_pipe_verify_loops_stored(void *p, int npairs, const svs_loop_pair *pairs, const void *params, svs_loop_result *results, int *match4_or_null,
+                                            long long match_rows)
+{
+    typedef svs::Pipeline<SVS_PIPE_KERNELS> Pipe;
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    if (npairs < 0 || (npairs > 0 && (!pairs || !results)) || !params) { g_err = "svs_pipe_verify_loops_stored: null argument"; return -1; }
+    try {
+        std::vector<Pipe::LoopPair> ps((size_t)npairs);
+        long long rows = 0;
+        for (int i = 0; i < npairs; ++i) {
+            ps[(size_t)i] = Pipe::LoopPair{ pairs[i].stream, (long)pairs[i].kf_id, (long)pairs[i].cand_kf_id };
+            const std::vector<int> *f = nullptr;
+            if (!h->pipe->KeyframeDescriptors(pairs[i].stream, (long)pairs[i].cand_kf_id, nullptr, &f)) { g_err = h->pipe->last_error(); return -1; }
+            rows += (long long)f->size();
+        }
+        if (match4_or_null && match_rows < rows) { g_err = "svs_pipe_verify_loops_stored: the match array is shorter than the candidates' descriptor rows"; return -1; }
+        std::vector<Pipe::LoopResult> rs;
+        if (!h->pipe->VerifyLoopsStored(ps, *static_cast<const svslam_loop_params *>(params), &rs)) { g_err = h->pipe->last_error(); return -1; }
+        size_t row = 0;
+        for (int i = 0; i < npairs; ++i) {
+            const Pipe::LoopResult &R = rs[(size_t)i];
+            svs_loop_result &o = results[i];
+            o.status = R.status; o.n_matches = R.n_matches; o.n_points = R.n_points; o.n_inliers = R.n_inliers; o.need_correction = R.need_correction ? 1 : 0; o.reserved = 0;
+            std::memcpy(o.T_corr, R.T_corr.v, 56); std::memcpy(o.T_rel, R.T_rel.v, 56); o.d = R.d;
+            const std::vector<int> *f = nullptr;
+            (void)h->pipe->KeyframeDescriptors(pairs[i].stream, (long)pairs[i].cand_kf_id, nullptr, &f);
+            if (match4_or_null) {
+                int *m = match4_or_null + 4 * row;
+                std::memset(m, 0, sizeof(int) * 4 * f->size());
+                for (int k = 0; k < R.n_matches; ++k) { m[4 * k] = R.match_c[(size_t)k]; m[4 * k + 1] = R.match_q[(size_t)k]; m[4 * k + 2] = R.match_dist[(size_t)k]; m[4 * k + 3] = R.match_inlier[(size_t)k]; }
+            }
+            row += f->size();
+        }
+        return 0;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
 extern "C" void *svs_pipe_backend_ctx(void *p) { return static_cast<PipeHandle *>(p)->kernels->backend_ctx(); }

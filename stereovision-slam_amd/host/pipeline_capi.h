@@ -97,6 +97,23 @@ typedef struct svs_loop_result {
     double T_corr[7], T_rel[7], d;
 } svs_loop_result;
 int svs_pipe_verify_loops(void *p, int nqueries, const svs_loop_query *queries, const void *params, svs_loop_result *results, int *match4_or_null);
+/* LoopClosure::ExtractKeypointsDescriptor (src/loopclosure.cpp:131-171) for every stream whose last step made a keyframe: BRIEF-256
+ * (svslam_brief_describe_batch) at the keyframe's non-outlier left features, stored with the keyframe (descriptor row -> feature
+ * index); one kernel call for all streams.  Call it after the step and before the next one: the keyframe's image is level 0 of a
+ * pyramid slot only until then.  brief_params_or_null: svslam_brief_params (include/svslam.h) or NULL for the default table, -1
+ * degree, edge 31.  Returns the number of keyframes described, -1 (svs_pipe_last_error, nothing stored): the map lives on the device
+ * (device_map = 1), the kernel's refusal.  Product library only. */
+int svs_pipe_describe_new_keyframes(void *p, const void *brief_params_or_null);
+/* the stored descriptors of keyframe kf_id: desc32 [n][32] and feat [n] = index of each row's feature in the keyframe's left list.
+ * Returns n (nothing is written when cap < n or an array is NULL: call again), -1 for a bad stream / id or a keyframe that was never
+ * described (a keyframe described with zero rows returns 0). */
+long long svs_pipe_keyframe_descriptors(void *p, int stream, long long kf_id, uint8_t *desc32, int *feat, long long cap);
+/* svs_pipe_verify_loops on the stored descriptors of both keyframes of every pair.  match4_or_null has match_rows rows of 4 ints: at
+ * least the sum of the candidate keyframes' descriptor rows, laid out as svs_pipe_verify_loops does.  -1 (nothing done): what
+ * svs_pipe_verify_loops refuses, a keyframe that was never described, a match array that is too short. */
+typedef struct svs_loop_pair { int stream; long long kf_id, cand_kf_id; } svs_loop_pair;
+int svs_pipe_verify_loops_stored(void *p, int npairs, const svs_loop_pair *pairs, const void *params, svs_loop_result *results, int *match4_or_null,
+                                 long long match_rows);
 /* on != 0: keyframes that leave the window from now on keep their feature lists, as the reference's do (svs_pipe_verify_loops
  * reads the candidate keyframe's; a keyframe whose lists were released is refused there).  Off by default. */
 int svs_pipe_keep_keyframe_features(void *p, int on);

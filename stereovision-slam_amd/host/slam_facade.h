@@ -268,12 +268,18 @@ struct FrontendOptions {            // the hyper-parameters Frontend::Frontend()
     // `pose_xtol: 0` in the YAML (or this field) = g2o's schedule to the last trial (src/frontend.cpp:482-493 as written);
     // 1e-9 trades the last digits of the pose for a fifth of the kernel's time.
     double pose_xtol = 1e-12;
+    // 1: every keyframe is described right after its step (Pipeline::DescribeNewKeyframes: BRIEF-256 at its non-outlier left
+    // features, LoopClosure::ExtractKeypointsDescriptor) and keyframes keep their feature lists when they leave the window, so
+    // that VerifyLoop(kf, cand, out) needs no descriptors from the caller.  `loop_descriptors: 1` in the YAML (or this field);
+    // 0 (default): nothing is described, behaviour and memory as without the key.  Needs the host map (device_map: 0).
+    int loop_descriptors = 0;
     static FrontendOptions FromConfig(const ConfigFile &c)
     {
         FrontendOptions o;
         o.device_map = (int)c.Num("device_map", o.device_map);
         o.low_latency = (int)c.Num("low_latency", o.low_latency);
         o.pose_xtol = c.Num("pose_xtol", o.pose_xtol);
+        o.loop_descriptors = (int)c.Num("loop_descriptors", o.loop_descriptors);
         o.num_features = (int)c.Num("num_features", o.num_features);
         o.num_features_init = (int)c.Num("num_features_init", o.num_features_init);
         o.num_features_tracking = (int)c.Num("num_features_tracking", o.num_features_tracking);
@@ -290,6 +296,9 @@ struct FrontendOptions {            // the hyper-parameters Frontend::Frontend()
 // does the kernel provider offer a device-resident map (HipKernels::kHasDeviceMap)?  The CPU twin's provider does not.
 template <class K> constexpr auto provider_has_device_map(int) -> decltype(K::kHasDeviceMap) { return K::kHasDeviceMap; }
 template <class K> constexpr bool provider_has_device_map(long) { return false; }
+// does it offer the descriptor kernel (HipKernels::brief_describe)?  The providers of the CPU twins do not.
+template <class K> constexpr auto provider_has_brief(int) -> decltype(&K::brief_describe, true) { return true; }
+template <class K> constexpr bool provider_has_brief(long) { return false; }
 
 template <class K>
 class FrontendT {
@@ -332,6 +341,7 @@ public:
         if (frame->is_keyframe_) frame->keyframe_id_ = (unsigned long)res.keyframe_id;
         frame->n_features_ = res.n_features; frame->n_inliers_ = res.n_inliers;
         status_ = (FrontendStatus)res.status;
+        if (frame->is_keyframe_ && opt_.loop_descriptors) describe_new_keyframe();
         if (frame->is_keyframe_ && loopclosure_) loopclosure_(frame);
         if (viewer_) viewer_(frame);
         last_frame_ = current_frame_;
@@ -358,10 +368,28 @@ public:
         if (out) *out = res[0];
         return true;
     }
+    // the same on the descriptors stored for both keyframes (`loop_descriptors: 1`); false also for a keyframe that was never described
+    bool VerifyLoop(unsigned long kf_id, unsigned long cand_kf_id, const svslam_loop_params &params, typename Pipeline<K>::LoopResult *out)
+    {
+        if (!pipe_) return false;
+        std::vector<typename Pipeline<K>::LoopResult> res;
+        if (!pipe_->VerifyLoopsStored({ typename Pipeline<K>::LoopPair{ 0, (long)kf_id, (long)cand_kf_id } }, params, &res)) return false;
+        if (out) *out = res[0];
+        return true;
+    }
     K *kernels() { return kernels_.get(); }
     bool LowLatency() const { return opt_.low_latency != 0; }
 
 private:
+    // (a function of its own so that a provider without the kernel never instantiates Pipeline::DescribeNewKeyframes)
+    void describe_new_keyframe()
+    {
+        if constexpr (provider_has_brief<K>(0)) {
+            if (!pipe_->DescribeNewKeyframes()) throw SLAMException(pipe_->last_error());
+        } else {
+            throw SLAMException("loop_descriptors: this kernel provider has no descriptor kernel");
+        }
+    }
     void create(int w, int h)
     {
         if (!camera_left_ || !camera_right_) throw SLAMException("Frontend: SetCameras before the first AddFrame");
@@ -392,6 +420,7 @@ private:
         if (kernels_->set_low_latency(opt_.low_latency ? 1 : 0) != 0) throw SLAMException(std::string("low-latency shapes: ") + kernels_->last_error());
         if (kernels_->set_pose_only_xtol(opt_.pose_xtol) != 0) throw SLAMException(std::string("pose_xtol: ") + kernels_->last_error());
         pipe_.reset(new Pipeline<K>(cfg, *kernels_, 1, 1));
+        if (opt_.loop_descriptors) pipe_->SetKeepKeyframeFeatures(true);
         wire_backend(); wire_map();
     }
     void unwire()
@@ -553,6 +582,10 @@ public:
     bool VerifyLoop(unsigned long kf_id, unsigned long cand_kf_id, int nq, const uint8_t *desc_q, const int *feat_q, int nc,
                     const uint8_t *desc_c, const int *feat_c, typename Pipeline<K>::LoopResult *out, unsigned seed = 0)
     {
+        return frontend_->VerifyLoop(kf_id, cand_kf_id, nq, desc_q, feat_q, nc, desc_c, feat_c, loop_params(seed), out);
+    }
+    svslam_loop_params loop_params(unsigned seed) const
+    {
         svslam_loop_params p;
         std::memset(&p, 0, sizeof(p));
         p.min_matches = (int)config_.Num("min_num_acceptable_keypoint_match", 20);
@@ -560,7 +593,12 @@ public:
         p.max_pose_distance = config_.Num("max_pose_distance_between_loop_keyframes", 20);
         p.min_pose_difference = config_.Num("min_pose_differnece_between_old_new", 1);
         p.max_pose_difference = config_.Num("max_pose_differnece_between_old_new", 50);
-        return frontend_->VerifyLoop(kf_id, cand_kf_id, nq, desc_q, feat_q, nc, desc_c, feat_c, p, out);
+        return p;
+    }
+    // the same on the descriptors stored for both keyframes (`loop_descriptors: 1` in the configuration file)
+    bool VerifyLoop(unsigned long kf_id, unsigned long cand_kf_id, typename Pipeline<K>::LoopResult *out, unsigned seed = 0)
+    {
+        return frontend_->VerifyLoop(kf_id, cand_kf_id, loop_params(seed), out);
     }
     FrontendStatus GetFrontendStatus() const { return frontend_->GetStatus(); }
     // keyframes.txt + landmarks.pcd under output_dir (:198-310; the reference adds a time-stamped folder)

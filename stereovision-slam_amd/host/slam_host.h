@@ -94,6 +94,12 @@ struct Frame {
     SE3 loop_relative_pose;           // keyframe a loop detector matched this one with, and T_this * T_loop^-1 as it measured it
     int ba_local = -1;                // index in the current BA problem (scratch of Backend::Optimize)
     int dslot = -1;                   // device_map: slot of this keyframe in the provider's window arena
+    // descriptor_ / desc_feat_indx_ of the reference (LoopClosure::ExtractKeypointsDescriptor): 32 bytes a row, and the index in
+    // `left` of the feature each row describes.  Empty until Pipeline::DescribeNewKeyframes is asked; kept when the keyframe leaves
+    // the window.  described: the keyframe was described (possibly with zero rows)
+    std::vector<uint8_t> desc;
+    std::vector<int> desc_feat_indx;
+    bool described = false;
 };
 
 struct ObsRef {
@@ -807,6 +813,87 @@ public:
         }
         if (pose7) std::memcpy(pose7, kfs[(size_t)kf_id]->pose.v, 56);
         return true;
+    }
+    // LoopClosure::ExtractKeypointsDescriptor (src/loopclosure.cpp:131-171) for every stream whose last step made a keyframe that has
+    // no descriptors yet: BRIEF-256 (svslam_brief_describe_batch) at the non-outlier left features (:142-148) of the
+    // keyframe, on level 0 of slot_cur, where the keyframe's left image still is until the stream's next step.  ONE provider call
+    // for all streams.  Frame::desc_feat_indx[row] is the feature's own index: the reference recovers it by comparing positions
+    // (:154-165), which maps two features at one pixel to the first of them.  The reference describes in its loop-closure thread,
+    // some frames later, when the backend may have flagged more outliers; here it is right after the keyframe's step.  A local BA
+    // in flight is collected first (the provider's context is its until then).  params: nullptr for the default table, -1 degree,
+    // edge 31.  n_described (optional): keyframes described by this call.  False (last_error(), nothing stored): device_map = 1,
+    // the provider's refusal (e.g. more than 1024 non-outlier features).
+    bool DescribeNewKeyframes(const svslam_brief_params *params = nullptr, int *n_described = nullptr)
+    {
+        if (n_described) *n_described = 0;
+        if (device_map()) return refuse("DescribeNewKeyframes: with device_map = 1 the keyframes' features live on the device; not supported yet");
+        Flush();
+        std::vector<Frame *> kfs;
+        std::vector<svslam_brief_job> jobs;
+        std::vector<std::vector<int>> sel;
+        std::vector<float> xy;
+        for (auto &stp : streams_) {
+            Frame *f = stp->last;
+            if (!f || !f->is_keyframe || f->described) continue;
+            svslam_brief_job J;
+            std::memset(&J, 0, sizeof(J));
+            J.slot = stp->slot_cur; J.pt_ofs = (int)(xy.size() / 2);
+            sel.emplace_back();
+            for (size_t i = 0; i < f->left.size(); ++i)
+                if (!f->left[i].outlier) { sel.back().push_back((int)i); xy.push_back(f->left[i].x); xy.push_back(f->left[i].y); }
+            J.npts = (int)sel.back().size();
+            jobs.push_back(J); kfs.push_back(f);
+        }
+        if (kfs.empty()) return true;
+        svslam_brief_params P;
+        if (params) P = *params; else { P.pattern = nullptr; P.angle_deg = -1.0f; P.edge = 31; }
+        const int total = (int)(xy.size() / 2);
+        std::vector<uint8_t> desc(32 * (size_t)total + 1);
+        std::vector<int> dpt((size_t)total + 1);
+        if (k_.brief_describe((int)jobs.size(), jobs.data(), &P, total, xy.data(), desc.data(), dpt.data()) != 0)
+            return refuse(std::string("DescribeNewKeyframes: ") + k_.last_error());
+        for (size_t j = 0; j < kfs.size(); ++j) {
+            Frame *f = kfs[j];
+            const svslam_brief_job &J = jobs[j];
+            f->desc.assign(desc.begin() + 32 * (size_t)J.pt_ofs, desc.begin() + 32 * ((size_t)J.pt_ofs + (size_t)J.n_desc));
+            f->desc_feat_indx.resize((size_t)J.n_desc);
+            for (int r = 0; r < J.n_desc; ++r) f->desc_feat_indx[(size_t)r] = sel[j][(size_t)dpt[(size_t)J.pt_ofs + (size_t)r]];
+            f->described = true;
+        }
+        if (n_described) *n_described = (int)kfs.size();
+        return true;
+    }
+    // the stored descriptors of a keyframe, read-only: rows of 32 bytes and desc_feat_indx.  False: a bad stream / id, or a keyframe
+    // that was never described (which is not a keyframe described with zero rows)
+    bool KeyframeDescriptors(int s, long kf_id, const std::vector<uint8_t> **desc, const std::vector<int> **feat)
+    {
+        if (s < 0 || s >= nstreams()) return refuse("KeyframeDescriptors: no such stream");
+        const std::vector<Frame *> &kfs = streams_[s]->map.keyframes_;
+        if (kf_id < 0 || kf_id >= (long)kfs.size()) return refuse("KeyframeDescriptors: not a keyframe id of this stream");
+        const Frame *f = kfs[(size_t)kf_id];
+        if (!f->described) return refuse("KeyframeDescriptors: the keyframe was never described (DescribeNewKeyframes after its step)");
+        if (desc) *desc = &f->desc;
+        if (feat) *feat = &f->desc_feat_indx;
+        return true;
+    }
+    // VerifyLoops on the descriptors DescribeNewKeyframes stored: the queries are built from Frame::desc / desc_feat_indx of both
+    // keyframes and handed to VerifyLoops unchanged.  False (nothing done): what VerifyLoops refuses, and a keyframe that was never
+    // described.
+    struct LoopPair { int stream; long kf_id, cand_kf_id; };
+    bool VerifyLoopsStored(const std::vector<LoopPair> &pairs, const svslam_loop_params &params, std::vector<LoopResult> *results)
+    {
+        std::vector<LoopQuery> qs;
+        for (const LoopPair &p : pairs) {
+            if (p.stream < 0 || p.stream >= nstreams()) return refuse("VerifyLoopsStored: no such stream");
+            const std::vector<Frame *> &kfs = streams_[p.stream]->map.keyframes_;
+            if (p.kf_id < 0 || p.kf_id >= (long)kfs.size() || p.cand_kf_id < 0 || p.cand_kf_id >= (long)kfs.size())
+                return refuse("VerifyLoopsStored: not a keyframe id of this stream");
+            const Frame *q = kfs[(size_t)p.kf_id], *c = kfs[(size_t)p.cand_kf_id];
+            if (!q->described || !c->described) return refuse("VerifyLoopsStored: a keyframe of the pair was never described (DescribeNewKeyframes after its step)");
+            const int nq = (int)q->desc_feat_indx.size(), nc = (int)c->desc_feat_indx.size();
+            qs.push_back(LoopQuery{ p.stream, p.kf_id, p.cand_kf_id, nq, q->desc.data(), nq, q->desc_feat_indx.data(), nc, c->desc.data(), nc, c->desc_feat_indx.data() });
+        }
+        return VerifyLoops(qs, params, results);
     }
     const std::string &last_error() const { return refusal_; }
 

@@ -93,6 +93,10 @@ class LoopResult(C.Structure):
                 ("reserved", C.c_int), ("T_corr", C.c_double * 7), ("T_rel", C.c_double * 7), ("d", C.c_double)]
 
 
+class LoopPair(C.Structure):
+    _fields_ = [("stream", C.c_int), ("kf_id", C.c_longlong), ("cand_kf_id", C.c_longlong)]
+
+
 def _bind(L):
     L.svs_pipe_create.restype = C.c_void_p
     L.svs_pipe_create.argtypes = [C.POINTER(PipeConfig), C.c_int, C.c_int]
@@ -120,6 +124,11 @@ def _bind(L):
         L.svs_pipe_keep_keyframe_features.argtypes = [C.c_void_p, C.c_int]
         L.svs_pipe_keyframe_features.restype = C.c_longlong
         L.svs_pipe_keyframe_features.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p]
+    if hasattr(L, "svs_pipe_describe_new_keyframes"):
+        L.svs_pipe_describe_new_keyframes.argtypes = [C.c_void_p, C.c_void_p]
+        L.svs_pipe_keyframe_descriptors.restype = C.c_longlong
+        L.svs_pipe_keyframe_descriptors.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong]
+        L.svs_pipe_verify_loops_stored.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
     return L
 
 
@@ -274,6 +283,69 @@ class Pipeline:
                             need_correction=bool(r.need_correction), T_corr=np.array(r.T_corr), T_rel=np.array(r.T_rel), d=r.d,
                             matches=m4[row:row + r.n_matches].astype(np.int64)))
             row += len(keep[i][2])
+        return out
+
+    def describe_new_keyframes(self, pattern=None, angle_deg=-1.0, edge=31):
+        """LoopClosure::ExtractKeypointsDescriptor for every stream whose last step made a keyframe (svs_pipe_describe_new_keyframes):
+        BRIEF-256 at the keyframe's non-outlier left features, stored with the keyframe.  Call it after step() and before the next
+        one.  pattern / angle_deg / edge: as Context.brief_describe.  Returns the number of keyframes described."""
+        import importlib
+        _svs = importlib.import_module(__package__)
+        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
+        if pat is not None and pat.size != 1024:
+            raise ValueError("describe_new_keyframes: the table has %d entries, not 256 x 4" % pat.size)
+        P = _svs.BriefParams(None if pat is None else pat.ctypes.data, float(angle_deg), int(edge))
+        n = self.L.svs_pipe_describe_new_keyframes(self.h, C.byref(P))
+        if n < 0:
+            raise RuntimeError("svs_pipe_describe_new_keyframes refused: " + self.L.svs_pipe_last_error().decode())
+        return n
+
+    def keyframe_descriptors(self, stream, kf_id):
+        """the stored descriptors of a keyframe (svs_pipe_keyframe_descriptors): desc [n, 32] u8 and feat [n] int32, the index of each
+        row's feature in keyframe_features(stream, kf_id).  Raises for a keyframe that was never described."""
+        n = self.L.svs_pipe_keyframe_descriptors(self.h, stream, C.c_longlong(kf_id), None, None, 0)
+        if n < 0:
+            raise RuntimeError("svs_pipe_keyframe_descriptors refused: " + self.L.svs_pipe_last_error().decode())
+        desc = np.zeros((n, 32), np.uint8); feat = np.zeros(n, np.int32)
+        if n and self.L.svs_pipe_keyframe_descriptors(self.h, stream, C.c_longlong(kf_id), desc.ctypes.data_as(C.c_void_p),
+                                                      feat.ctypes.data_as(C.c_void_p), n) != n:
+            raise RuntimeError("svs_pipe_keyframe_descriptors changed size between two calls")
+        return desc, feat
+
+    def verify_loops_stored(self, pairs, **params):
+        """verify_loops on the descriptors describe_new_keyframes stored (svs_pipe_verify_loops_stored).  pairs: (stream, kf_id,
+        cand_kf_id) each.  params and the result: as verify_loops."""
+        import importlib
+        _svs = importlib.import_module(__package__)
+        unknown = set(params) - set(_svs.LOOP_DEFAULTS)
+        if unknown:
+            raise TypeError("verify_loops_stored: unknown parameter(s) %s" % sorted(unknown))
+        p = dict(_svs.LOOP_DEFAULTS); p.update(params)
+        n = len(pairs)
+        ps = (LoopPair * max(n, 1))()
+        for i, (s, kf, cand) in enumerate(pairs):
+            ps[i] = LoopPair(int(s), int(kf), int(cand))
+        P = _svs.LoopParams((C.c_double * 4)(), (C.c_double * 7)(), int(p["min_matches"]), int(p["ransac_iters"]), float(p["reproj_px"]),
+                            float(p["max_pose_distance"]), float(p["min_pose_difference"]), float(p["max_pose_difference"]),
+                            int(p["seed"]) & 0xFFFFFFFF, 0)
+        rows_of = []
+        for s, kf, cand in pairs:
+            k = self.L.svs_pipe_keyframe_descriptors(self.h, int(s), C.c_longlong(int(cand)), None, None, 0)
+            if k < 0:
+                raise RuntimeError("svs_pipe_verify_loops_stored refused: " + self.L.svs_pipe_last_error().decode())
+            rows_of.append(k)
+        rows = sum(rows_of)
+        res = (LoopResult * max(n, 1))()
+        m4 = np.zeros((max(rows, 1), 4), np.int32)
+        if self.L.svs_pipe_verify_loops_stored(self.h, n, ps, C.byref(P), res, m4.ctypes.data_as(C.c_void_p), rows) != 0:
+            raise RuntimeError("svs_pipe_verify_loops_stored refused: " + self.L.svs_pipe_last_error().decode())
+        out = []; row = 0
+        for i in range(n):
+            r = res[i]
+            out.append(dict(status=r.status, n_matches=r.n_matches, n_points=r.n_points, n_inliers=r.n_inliers,
+                            need_correction=bool(r.need_correction), T_corr=np.array(r.T_corr), T_rel=np.array(r.T_rel), d=r.d,
+                            matches=m4[row:row + r.n_matches].astype(np.int64)))
+            row += rows_of[i]
         return out
 
     def map_snapshot(self, stream=0):
