@@ -22,6 +22,11 @@ static std::string g_lv_err;
 
 extern "C" const char *emu_lv_error() { return g_lv_err.c_str(); }
 
+// pieces of a hypothesis on their own, each compared with the reference's function of the same name
+extern "C" int emu_lv_draw4(unsigned seed, int i, int np, int *idx) { return lv_draw4(seed, i, np, idx) ? 1 : 0; }
+extern "C" void emu_lv_R_to_T(const double *Rt, double *T) { lv_R_to_T(Rt, T); }
+extern "C" int emu_lv_p3p(const double *X, const double *f, double *out) { return lv_p3p(X, f, out); }
+
 extern "C" int emu_loop_verify(int njobs, EmuLoopJob *jobs, const EmuLoopParams *prm, int total_c, const uint8_t *desc_c, const double *xyz_c,
                                const uint8_t *has_xyz, int total_q, const uint8_t *desc_q, const float *uv_q, int *match_c, int *match_q,
                                int *match_dist, uint8_t *match_inlier)

@@ -216,6 +216,15 @@ def hypothesis(cam, xyz, uv, seed, i):
     return best
 
 
+def quat_branch(R):
+    """which of R_to_T's four branches a rotation takes: 1 (trace > 0), 2, 3, 4 (the largest diagonal element is R[0], R[4], R[8])"""
+    if (R[0] + R[4]) + R[8] > 0.0:
+        return 1
+    if R[0] > R[4] and R[0] > R[8]:
+        return 2
+    return 3 if R[4] > R[8] else 4
+
+
 def R_to_T(R, t):
     tr = (R[0] + R[4]) + R[8]
     if tr > 0.0:
@@ -265,16 +274,23 @@ def _residuals(cam, T, xyz, uv):
     return pc, ex, ey
 
 
+def jacobian(cam, pc):
+    """d(ex, ey) / d(delta) of T <- exp(delta) T at delta = 0 (delta = translation, rotation), per point in the camera frame: J0, J1 [n, 6]"""
+    X, Y, Z = pc[:, 0], pc[:, 1], pc[:, 2]
+    Zi = 1.0 / Z; Zi2 = Zi * Zi; fx, fy = cam[0], cam[1]; o = np.zeros_like(X)
+    J0 = np.stack([-fx * Zi, o, fx * X * Zi2, fx * X * Y * Zi2, -fx - fx * X * X * Zi2, fx * Y * Zi], axis=1)
+    J1 = np.stack([o, -fy * Zi, fy * Y * Zi2, fy + fy * Y * Y * Zi2, -fy * X * Y * Zi2, -fy * X * Zi], axis=1)
+    return J0, J1
+
+
 def refine(cam, T, xyz, uv, iters=LM_ITERS, stats=None):
-    """g2o's Levenberg-Marquardt (ref_pose_graph.optimize's control flow) on the 6 parameters of T <- exp(d) T"""
+    """g2o's Levenberg-Marquardt (ref_pose_graph.optimize's control flow) on the 6 parameters of T <- exp(d) T.
+    stats (a list) receives one (iteration, lambda, cost before, cost of the trial, rho, accepted) per trial"""
     T = np.array(T, np.float64)
     lam = 0.0; nu = 2.0
     for it in range(iters):
         pc, ex, ey = _residuals(cam, T, xyz, uv)
-        X, Y, Z = pc[:, 0], pc[:, 1], pc[:, 2]
-        Zi = 1.0 / Z; Zi2 = Zi * Zi; fx, fy = cam[0], cam[1]; o = np.zeros_like(X)
-        J0 = np.stack([-fx * Zi, o, fx * X * Zi2, fx * X * Y * Zi2, -fx - fx * X * X * Zi2, fx * Y * Zi], axis=1)
-        J1 = np.stack([o, -fy * Zi, fy * Y * Zi2, fy + fy * Y * Y * Zi2, -fy * X * Y * Zi2, -fy * X * Zi], axis=1)
+        J0, J1 = jacobian(cam, pc)
         H = J0.T @ J0 + J1.T @ J1
         b = -(J0.T @ ex + J1.T @ ey)
         cur = float(np.sum(ex * ex + ey * ey))
@@ -319,7 +335,8 @@ def _norm6(x):
 def loop_verify(job, cam, ext_l, detail=None, **params):
     """job: dict(desc_c [nc, 32] u8, desc_q [nq, 32] u8, xyz_c [nc, 3], has_xyz [nc], uv_q [nq, 2] f32, T_cur[7], T_cand[7]).
     returns dict(status, n_matches, n_points, n_inliers, T_corr, T_rel, d, need_correction, matches [n, 4] = candidate row, current
-    row, distance, inlier flag).  detail (a dict) receives what the case margins are asserted on."""
+    row, distance, inlier flag).  detail (a dict) receives what the case margins are asserted on: the hypotheses, the winner, the branch
+    of R_to_T it took (quat_branch), the LM's trial list (lm) and what the LM ran on (T_start, xyz, uv, inl)."""
     p = dict(DEFAULTS); p.update(params)
     cam = [float(v) for v in cam]; ext_l = np.asarray(ext_l, np.float64)
     desc_c = np.asarray(job["desc_c"], np.uint8).reshape(-1, 32); desc_q = np.asarray(job["desc_q"], np.uint8).reshape(-1, 32)
@@ -370,7 +387,9 @@ def loop_verify(job, cam, ext_l, detail=None, **params):
     matches[pm, 3] = inl
     if bc < p["min_matches"]:
         return out
-    T = refine(cam, R_to_T(R, t), xyz[inl], uv[inl])
+    lm = []
+    T = refine(cam, R_to_T(R, t), xyz[inl], uv[inl], stats=lm)
+    detail.update(lm=lm, quat_branch=quat_branch(R), T_start=R_to_T(R, t), xyz=xyz, uv=uv, inl=inl)
     T_corr = se3_mul(se3_inv(ext_l), T)
     T_rel = se3_mul(T_corr, se3_inv(np.asarray(job["T_cand"], np.float64)))
     out["T_corr"] = T_corr; out["T_rel"] = T_rel

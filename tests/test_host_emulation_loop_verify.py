@@ -1,10 +1,10 @@
 """csrc/k_loop_verify.h itself, compiled for the host (tests/cpp/lv_host_emu, -ffp-contract=off), against tests/ref_loop_verify.py over
 every case of loop_verify_cases.py: the Hamming scan, the order-keeping compaction, the hash, the P3P, the inlier counts, the winner,
-the LM and the gates are checked here without a device.  Not a replacement for tests/test_gpu_loop_verify.py: the compiler, the ISA,
+the LM and the gates are checked here without a device; lv_draw4, lv_R_to_T and lv_p3p also on their own, against the reference's
+function of the same name.  The cases with pixel noise are admitted only where this build stays within a tenth of the tolerances: an
+unconverged LM amplifies rounding, and the device (whose sin / cos / atan differ) is compared at the whole.  Not a replacement for tests/test_gpu_loop_verify.py: the compiler, the ISA,
 the barriers, LDS and the launch are not in it."""
-import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,15 +13,11 @@ import loop_verify_cases as lc
 import ref_loop_verify as rl
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU = os.path.join(ROOT, "tests", "cpp", "lv_host_emu")
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    d = tmp_path_factory.mktemp("lv_host_emu")
-    so = str(d / "liblv_host_emu.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(EMU, "emu.cpp"), "-o", so])
-    return C.CDLL(so)
+    return lc.emu_build(ROOT, tmp_path_factory.mktemp("lv_host_emu"))
 
 
 @pytest.mark.parametrize("name", list(lc.CASES))
@@ -31,6 +27,21 @@ def test_kernel_source_on_the_host_against_the_reference(emu, name):
     ok, msg = lc.compare(got, ref)
     print(name, rl.STATUS_NAMES[ref["status"]], msg)
     assert ok, msg
+    if name in lc.NEW:                                          # a tenth of the tolerances; a seed that misses it is replaced
+        ok, msg = lc.compare(got, ref, share=0.1)
+        assert ok, msg
+
+
+def test_draw4_against_the_reference(emu):
+    lc.check_draw4(emu)
+
+
+def test_R_to_T_against_the_reference_in_every_branch(emu):
+    lc.check_R_to_T(emu)
+
+
+def test_p3p_against_the_reference(emu):
+    lc.check_p3p(emu)
 
 
 def test_a_job_does_not_depend_on_the_jobs_it_shares_a_call_with(emu):
