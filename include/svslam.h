@@ -433,6 +433,58 @@ int svslam_brief_describe_batch(svslam_ctx *ctx, int njobs, svslam_brief_job *jo
                                 int total_pts, const float *xy, uint8_t *desc /* [total_pts][32] */, int *desc_pt /* [total_pts] */);
 int svslam_brief_default_pattern(int8_t out[1024]);
 
+/* ---- loop candidate search: a resident store of global image descriptors and the two-threshold rule ----------
+ * Replaces stage 1 of the reference's loop closure, LoopClosure::LoopKeyframeCandidate (src/loopclosure.cpp:227-284) with
+ * SimilarityScore (:173-180) and the normalisation of :128.  The global descriptor itself (the reference's MobileNetV2 vector of 1280
+ * floats) is an INPUT; any vector of dim floats, 1 <= dim <= 4096, serves.  The store lives in the context, on the device:
+ * nstreams x capacity normalised rows with their keyframe ids, ascending per stream.  Its layout is opaque.
+ * The contract, met bit for bit by the kernel, its host build and tests/ref_loop_candidates.py; no tolerance anywhere:
+ *   similarity  of two f32 vectors: 64 accumulators start at +0; accumulator l takes the elements e = l, l + 64, l + 128, ... below
+ *               dim in that order, each step acc = acc + (a[e] * b[e]) with the product rounded to f32 and then the sum (no FMA);
+ *               then six halving steps s = 32, 16, 8, 4, 2, 1: acc[l] += acc[l + s] for l < s; the similarity is acc[0].
+ *   normalise   n2 = similarity(a, a); v[e] = a[e] / sqrtf(n2), IEEE square root and division.  n2 zero or not finite (a zero vector,
+ *               an infinity or NaN in it, an overflow or underflow of the sum) is BAD_VECTOR; the reference would store NaNs.
+ *               Stored rows are normalised at the append, a query inside the search call.
+ *   selection   over the stream's stored rows in ascending keyframe id: a row with kf_id - id < min_gap is skipped (the reference
+ *               hard-codes 20); best = the largest similarity that is > 0, the lowest id on a tie; n_weak counts the compared rows
+ *               with sim > weak, strictly, the best included; n_compared counts the compared rows.  Then, in this order:
+ *               NONE           no compared row has sim > 0 (the reference would fetch keyframe 0 and insert a null there)
+ *               BELOW_STRONG   best < strong
+ *               TOO_MANY_WEAK  n_weak > max_num_weak
+ *               FOUND          otherwise; cand_kf = the best's id.
+ *               Every output is defined for every status: cand_kf is -1 unless FOUND; best_sim / best_kf are 0 / -1 for NONE and
+ *               BAD_VECTOR and the best otherwise; BAD_VECTOR (the query) has n_weak = n_compared = 0.
+ * Against the reference: Eigen's vectorised a.transpose() * b sums in another order, so a similarity can differ from the reference's
+ * by rounding, within (ceil(dim / 64) + 7) 2^-24 sum |a b| of the exact dot product each (tests/test_ref_loop_candidates.py derives
+ * the bound); a threshold decision that close to the threshold can come out differently.
+ *
+ * svslam_loopdb_configure  allocates (or re-allocates) the store and empties it.  Refused: nstreams < 1, capacity < 1, dim outside
+ *                          1 .. 4096; no device memory, which leaves the old store as it was.
+ * svslam_loopdb_append_batch  normalises n vectors (vecs [n][dim]) and appends row i to streams[i] under kf_ids[i]; a stream may come
+ *                          more than once in a call.  Refused as a whole, nothing written: an unknown stream, a negative id, an id not
+ *                          above the stream's last one, a full stream, a BAD_VECTOR.  n == 0 is a valid no-op.
+ * svslam_loop_candidates_batch  one job per stream per call, streams strictly ascending; vecs [njobs][dim] are the raw queries.
+ *                          Refused, nothing written: an unconfigured store, an unknown or repeated or descending stream, a kf_id not
+ *                          above the stream's last stored id, min_gap < 0, max_num_weak < 0, a threshold that is not finite.
+ *                          njobs == 0 is a valid no-op.  A BAD_VECTOR query is that job's status, not a refusal.  A job's result does
+ *                          not depend on the other jobs of the call; two calls on the same inputs give the same bits.
+ * svslam_loopdb_count      the rows a stream holds.
+ * svslam_loopdb_read       the first min(count, max_rows) ids and normalised rows of a stream, rows in the vector's own order.
+ * The reference's thresholds (tests/golden/config-00.yaml): weak 0.93, strong 0.95, max_num_weak 3; min_gap 20. */
+enum { SVSLAM_LC_FOUND = 0, SVSLAM_LC_NONE = 1, SVSLAM_LC_BELOW_STRONG = 2, SVSLAM_LC_TOO_MANY_WEAK = 3, SVSLAM_LC_BAD_VECTOR = 4 };
+typedef struct svslam_lc_job {
+    int stream, kf_id;                                        /* in */
+    int status, cand_kf, best_kf, n_weak, n_compared;         /* out */
+    float best_sim;                                           /* out */
+} svslam_lc_job;
+typedef struct svslam_lc_params { float weak, strong; int max_num_weak, min_gap; } svslam_lc_params;
+int svslam_loopdb_configure(svslam_ctx *ctx, int nstreams, int capacity, int dim);
+int svslam_loopdb_append_batch(svslam_ctx *ctx, int n, const int *streams, const int *kf_ids, const float *vecs /* [n][dim] */);
+int svslam_loop_candidates_batch(svslam_ctx *ctx, int njobs, svslam_lc_job *jobs, const svslam_lc_params *params,
+                                 const float *vecs /* [njobs][dim] */);
+int svslam_loopdb_count(svslam_ctx *ctx, int stream, int *count);
+int svslam_loopdb_read(svslam_ctx *ctx, int stream, int max_rows, int *kf_ids, float *vecs /* [max_rows][dim] */);
+
 /* ---- shared-map bundle adjustment (BASELINE config 5; not in the reference) -----------
  * ONE local-BA problem whose landmarks are sharded over the GPUs of a node: every rank holds all
  * nkf poses and its landmarks with their edges.  The rank opens its shard, then runs the pieces of
@@ -636,7 +688,8 @@ int svslam_sync(svslam_ctx *ctx);
  * the roofline entry.  family: 0 pyramid, 1 lk, 2 gftt, 3 triangulate,
  * 4 pose_only, 5 local_ba, 6 stereo_bm (units = jobs), 12 cloud_filter (units = points; appended
  * after the last number in use, nothing moved), 13 pose_graph (units = jobs; appended after 12, nothing moved),
- * 14 loop_verify (units = jobs; appended after 13, nothing moved), 15 brief (units = points; appended after 14, nothing moved).
+ * 14 loop_verify (units = jobs; appended after 13, nothing moved), 15 brief (units = points; appended after 14, nothing moved),
+ * 16 loop_candidates (units = rows compared, summed over the jobs; appended after 15, nothing moved).
  * Development families follow and are NOT stable numbers: with stereo_bm taking 6, the
  * per-kernel split moved from 6-9 to 7-10 and the local-BA solver interval from 10 to 11.
  * A caller that passed those raw numbers must move with them (Python addresses them by name). */

@@ -21,6 +21,7 @@ ABI_SYMBOLS = [
     "svslam_pyramid_batch", "svslam_pyramid_decimate_batch", "svslam_set_source_size", "svslam_set_low_latency", "svslam_set_pose_only_xtol", "svslam_get_pose_only_xtol", "svslam_pyramid_read",
     "svslam_pyramid_read_padded", "svslam_stereo_bm_batch", "svslam_stereo_bm_strip_rows", "svslam_dense_cloud_batch", "svslam_cloud_sor_batch", "svslam_cloud_voxel_grid", "svslam_debug_cloud_sor_climbs", "svslam_lk_batch", "svslam_gftt_batch", "svslam_gftt_eigmap", "svslam_triangulate_batch",
     "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect", "svslam_pose_graph_batch", "svslam_loop_verify_batch", "svslam_brief_describe_batch", "svslam_brief_default_pattern",
+    "svslam_loopdb_configure", "svslam_loopdb_append_batch", "svslam_loop_candidates_batch", "svslam_loopdb_count", "svslam_loopdb_read",
     "svslam_track_batch", "svslam_rtrack_batch", "svslam_rtrack_upload",
     "svslam_sba_io_doubles", "svslam_sba_open", "svslam_sba_phase", "svslam_sba_close",
     "svslam_device_count", "svslam_dmap_keyframe_batch", "svslam_dmap_ba_collect", "svslam_dmap_read", "svslam_dmap_evicted", "svslam_sba_comm_unique_id", "svslam_sba_comm_init", "svslam_sba_comm_destroy", "svslam_sba_solve",
@@ -37,14 +38,15 @@ DEBUG_FAMILIES = {"dbg0": 7, "dbg1": 8, "dbg2": 9, "dbg3": 10}     # per-kernel 
 KERNEL_FAMILIES = {"ba_solve": 11}
 CLOUD_FAMILIES = {"cloud_filter": 12}      # the outlier removal and the voxel grid of the dense program (units = points); appended, nothing renumbered
 # svslam_pose_graph_batch, svslam_loop_verify_batch (units = jobs), svslam_brief_describe_batch (units = points); appended after 12,
-# 13 and 14, nothing renumbered
-LOOP_FAMILIES = {"pose_graph": 13, "loop_verify": 14, "brief": 15}
+# 13 and 14, nothing renumbered; svslam_loop_candidates_batch (units = rows compared) appended after 15
+LOOP_FAMILIES = {"pose_graph": 13, "loop_verify": 14, "brief": 15, "loop_candidates": 16}
 # the HIP kernel(s) behind each timing family at the batch operating point (what a rocprofv3 --kernel-trace --stats row is named)
 FAMILY_KERNELS = {"pyramid": ["k_pyr_fused"], "lk": ["k_lk"], "gftt": ["k_gftt_eig3", "k_gftt_select2"], "triangulate": ["k_triangulate"],
                   "pose_only": ["k_pose_only"], "local_ba": ["k_dmap_ba_gather", "k_ba_build", "k_local_ba_t", "k_dmap_ba_scatter"],
                   "ba_solve": ["k_local_ba_t"], "stereo_bm": ["k_bm_fill", "k_stereo_bm", "k_dense_cloud"],
                   "cloud_filter": ["k_cf_keys", "k_cf_gather", "k_cf_knn", "k_vg_keys", "k_vg_heads", "k_vg_starts", "k_vg_reduce"],
-                  "pose_graph": ["k_pose_graph"], "loop_verify": ["k_loop_verify"], "brief": ["k_brief_filter", "k_brief_describe"]}
+                  "pose_graph": ["k_pose_graph"], "loop_verify": ["k_loop_verify"], "brief": ["k_brief_filter", "k_brief_describe"],
+                  "loop_candidates": ["k_lc_candidates"]}
 
 
 class Limits(C.Structure):
@@ -108,6 +110,21 @@ LOOP_STATUS = ("ACCEPTED", "FEW_MATCHES", "FEW_POINTS", "FEW_INLIERS", "TOO_FAR"
 # the reference's constants (src/loopclosure.cpp:381) and the values of its config for the loop keys
 LOOP_DEFAULTS = dict(min_matches=20, ransac_iters=100, reproj_px=5.991, max_pose_distance=20.0, min_pose_difference=1.0,
                      max_pose_difference=50.0, seed=0)
+
+
+class LcJob(C.Structure):
+    _fields_ = [("stream", C.c_int), ("kf_id", C.c_int), ("status", C.c_int), ("cand_kf", C.c_int), ("best_kf", C.c_int),
+                ("n_weak", C.c_int), ("n_compared", C.c_int), ("best_sim", C.c_float)]
+
+
+class LcParams(C.Structure):
+    _fields_ = [("weak", C.c_float), ("strong", C.c_float), ("max_num_weak", C.c_int), ("min_gap", C.c_int)]
+
+
+LC_STATUS = ("FOUND", "NONE", "BELOW_STRONG", "TOO_MANY_WEAK", "BAD_VECTOR")
+# potential_loop_weak_threshold, potential_loop_strong_threshold, max_num_weak_threshold of the reference's configuration; the gap is
+# the literal of src/loopclosure.cpp:244
+LC_DEFAULTS = dict(weak=0.93, strong=0.95, max_num_weak=3, min_gap=20)
 
 
 class BriefJob(C.Structure):
@@ -685,6 +702,60 @@ class Context:
         desc = np.zeros((total, 32), np.uint8); dpt = np.zeros(total, np.int32)
         self._chk(self.L.svslam_brief_describe_batch(self.h, n, arr, C.byref(P), total, _p(XY), _p(desc), _p(dpt)), "brief_describe")
         return [(desc[j.pt_ofs:j.pt_ofs + j.n_desc].copy(), dpt[j.pt_ofs:j.pt_ofs + j.n_desc].copy(), j.n_desc) for j in arr]
+
+    # ---- loop candidate search ---------------------------------------------------
+    def loopdb_configure(self, nstreams, capacity, dim=1280):
+        """allocate (or re-allocate) and empty the context's store of global descriptors (svslam_loopdb_configure)"""
+        self._chk(self.L.svslam_loopdb_configure(self.h, int(nstreams), int(capacity), int(dim)), "loopdb_configure")
+        self._lc_dim = int(dim)
+
+    def _lc_vecs(self, vecs, n, what):
+        dim = getattr(self, "_lc_dim", None)
+        if dim is None:
+            raise RuntimeError("%s: the store is not configured" % what)
+        v = np.ascontiguousarray(vecs, np.float32).reshape(-1, dim) if n else np.zeros((0, dim), np.float32)
+        if len(v) != n:
+            raise ValueError("%s: %d vectors of %d floats for %d rows" % (what, len(v), dim, n))
+        return v
+
+    def loopdb_append(self, streams, kf_ids, vecs):
+        """normalise and append vecs [n, dim]: row i to streams[i] under kf_ids[i] (svslam_loopdb_append_batch); refused as a whole"""
+        s = np.ascontiguousarray(streams, np.int32).reshape(-1); k = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
+        if len(s) != len(k):
+            raise ValueError("loopdb_append: %d streams and %d ids" % (len(s), len(k)))
+        v = self._lc_vecs(vecs, len(s), "loopdb_append")
+        self._chk(self.L.svslam_loopdb_append_batch(self.h, len(s), _p(s), _p(k), _p(v)), "loopdb_append")
+
+    def loop_candidates(self, jobs, vecs, **params):
+        """LoopClosure::LoopKeyframeCandidate for one keyframe per stream, all in one call (svslam_loop_candidates_batch).
+        jobs: [(stream, kf_id)], streams ascending; vecs [njobs, dim] raw global descriptors.
+        params: weak, strong, max_num_weak, min_gap (LC_DEFAULTS).
+        returns a list of dicts: status (index into LC_STATUS), cand_kf, best_sim, best_kf, n_weak, n_compared."""
+        unknown = set(params) - set(LC_DEFAULTS)
+        if unknown:
+            raise TypeError("loop_candidates: unknown parameter(s) %s" % sorted(unknown))
+        p = dict(LC_DEFAULTS); p.update(params)
+        n = len(jobs)
+        arr = (LcJob * max(n, 1))()
+        for i, (s, k) in enumerate(jobs):
+            arr[i].stream, arr[i].kf_id = int(s), int(k)
+        v = self._lc_vecs(vecs, n, "loop_candidates") if n else np.zeros((0, 1), np.float32)
+        P = LcParams(float(p["weak"]), float(p["strong"]), int(p["max_num_weak"]), int(p["min_gap"]))
+        self._chk(self.L.svslam_loop_candidates_batch(self.h, n, arr, C.byref(P), _p(v)), "loop_candidates")
+        return [dict(status=arr[i].status, cand_kf=arr[i].cand_kf, best_sim=np.float32(arr[i].best_sim), best_kf=arr[i].best_kf,
+                     n_weak=arr[i].n_weak, n_compared=arr[i].n_compared) for i in range(n)]
+
+    def loopdb_count(self, stream):
+        n = C.c_int(0)
+        self._chk(self.L.svslam_loopdb_count(self.h, int(stream), C.byref(n)), "loopdb_count")
+        return n.value
+
+    def loopdb_read(self, stream):
+        """(kf_ids [n] int32, rows [n, dim] float32): what a stream holds, normalised (svslam_loopdb_read)"""
+        n = self.loopdb_count(stream)
+        ids = np.zeros(n, np.int32); rows = np.zeros((n, self._lc_dim), np.float32)
+        self._chk(self.L.svslam_loopdb_read(self.h, int(stream), n, _p(ids), _p(rows)), "loopdb_read")
+        return ids, rows
 
     # ---- shared-map BA (one rank's shard; the LM driver is shared_ba.py) ---------
     def sba_open(self, cam_l, ext_l, cam_r, ext_r, poses, pts, okf, olm, ori, ouv, huber_delta=5.991):

@@ -48,6 +48,7 @@ typedef enum { ncclDouble = 8 } ncclDataType_t;
 #include "k_pose_graph.h"
 #include "k_loop_verify.h"
 #include "k_brief.h"
+#include "k_loop_candidates.h"
 
 #define SVSLAM_DMAP_CHUNK 512     /* keyframe jobs per svslam_dmap_keyframe_batch call the staging arena is sized for */
 #define SVSLAM_DMAP_EVICT_PER_JOB 512   /* evicted-landmark records per job of a call (shared by the call's jobs; the surplus waits) */
@@ -63,6 +64,7 @@ enum { FAM_PYR = 0, FAM_LK, FAM_GFTT, FAM_TRI, FAM_POSE, FAM_BA,
        FAM_PG,         // 13: "pose_graph", svslam_pose_graph_batch (units = jobs); appended, nothing moved
        FAM_LV,         // 14: "loop_verify", svslam_loop_verify_batch (units = jobs); appended, nothing moved
        FAM_BRIEF,      // 15: "brief", svslam_brief_describe_batch (units = points); appended, nothing moved
+       FAM_LC,         // 16: "loop_candidates", svslam_loop_candidates_batch (units = rows compared); appended, nothing moved
        FAM_COUNT };
 
 struct Timing {
@@ -117,6 +119,8 @@ struct svslam_ctx {
     struct { unsigned char *d = nullptr; size_t cap = 0; std::vector<unsigned char> h; } lv;
     // descriptors (svslam_brief_describe_batch): the same arrangement
     struct { unsigned char *d = nullptr; size_t cap = 0; std::vector<unsigned char> h; } br;
+    // loop candidates: the resident store of normalised global descriptors (S on the device, H its bookkeeping) and a call's staging
+    struct { LcStore S = {}; LcHost H; unsigned char *d = nullptr; size_t cap = 0; std::vector<unsigned char> h; } lc;
     // BA scratch
     BaWork bw;
     int bw_jobs = 0;          // problems per call the BA scratch holds
@@ -793,6 +797,7 @@ void svslam_destroy(svslam_ctx *c)
     (void)hipFree(c->pg.d);
     (void)hipFree(c->lv.d);
     (void)hipFree(c->br.d);
+    (void)hipFree(c->lc.d); (void)hipFree(c->lc.S.rows); (void)hipFree(c->lc.S.ids);
     ba_work_free(c->bw);
     ll_release(c);
     if (c->d_ba_prof) (void)hipFree(c->d_ba_prof);
@@ -2789,6 +2794,149 @@ int svslam_brief_describe_batch(svslam_ctx *c, int njobs, svslam_brief_job *jobs
     if (d2h_sync(c, 0, 0)) return -1;
     br_copy_out(Hb, njobs, in.data(), desc, desc_pt);
     for (int j = 0; j < njobs; ++j) jobs[j].n_desc = in[(size_t)j].n_desc;
+    return 0;
+}
+
+
+// ------------------------------------------------------------------ loop candidates: resident store and search
+namespace {
+// a call's staging: a struct array of head bytes, then n vectors of dim floats; grown on demand and kept
+int lc_stage(svslam_ctx *c, size_t bytes, const char *what)
+{
+    if (bytes > c->lc.cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(c->lc.d); c->lc.d = nullptr; c->lc.cap = 0;
+        const size_t want = bytes + bytes / 4;
+        if (hipMalloc(&c->lc.d, want) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, "%s: no device memory for %zu bytes", what, want);
+        }
+        c->lc.cap = want;
+    }
+    try { if (c->lc.h.size() < bytes) c->lc.h.resize(bytes); }
+    catch (const std::bad_alloc &) { return fail(c, "%s: no host memory for %zu bytes of staging", what, bytes); }
+    return 0;
+}
+inline size_t lc_head(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+}
+
+int svslam_loopdb_configure(svslam_ctx *c, int nstreams, int capacity, int dim)
+{
+    if (!c) return -1;
+    const char *why = lc_check_configure(nstreams, capacity, dim);
+    if (why) return fail(c, "loopdb_configure: %s", why);
+    if (arena_busy(c)) return -1;
+    const size_t nrows = (size_t)nstreams * (size_t)capacity, dp = (size_t)lc_padded(dim);
+    if (nrows > ((size_t)1 << 31) - 1 || nrows * dp > ((size_t)1 << 40) / sizeof(float)) return fail(c, "loopdb_configure: the store would pass 2^31 rows or 1 TiB");
+    float *rows = nullptr; int *ids = nullptr;
+    if (hipMalloc(&rows, nrows * dp * sizeof(float)) != hipSuccess || hipMalloc(&ids, nrows * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(rows);
+        return fail(c, "loopdb_configure: no device memory for %zu rows of %zu floats (the store is as it was)", nrows, dp);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(c->lc.S.rows); (void)hipFree(c->lc.S.ids);
+    c->lc.S = LcStore{ rows, ids, nstreams, capacity, dim, (int)dp };
+    lc_host_configure(c->lc.H, nstreams, capacity, dim);
+    return 0;
+}
+
+int svslam_loopdb_append_batch(svslam_ctx *c, int n, const int *streams, const int *kf_ids, const float *vecs)
+{
+    if (!c) return -1;
+    if (n < 0) return fail(c, "loopdb_append: negative count");
+    if (n && (!streams || !kf_ids || !vecs)) return fail(c, "loopdb_append: null array");
+    if (arena_busy(c)) return -1;
+    std::vector<LcApp> apps((size_t)n);
+    const char *why = lc_check_append(c->lc.H, n, streams, kf_ids, apps.data());
+    if (why) return fail(c, "loopdb_append: %s", why);
+    if (n == 0) return 0;
+    const size_t head = lc_head(sizeof(LcApp) * (size_t)n), vbytes = sizeof(float) * (size_t)n * c->lc.S.dim;
+    if (lc_stage(c, head + vbytes, "loopdb_append")) return -1;
+    memcpy(c->lc.h.data(), apps.data(), sizeof(LcApp) * (size_t)n);
+    memcpy(c->lc.h.data() + head, vecs, vbytes);
+    LcApp *d_apps = reinterpret_cast<LcApp *>(c->lc.d);
+    const float *d_vecs = reinterpret_cast<const float *>(c->lc.d + head);
+    HIPCHK(c, hipMemcpyAsync(c->lc.d, c->lc.h.data(), head + vbytes, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_lc_append, dim3(n), dim3(64), 0, c->stream, c->lc.S, d_apps, d_vecs, 0);        // which vectors can be normalised
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->lc.h.data(), c->lc.d, sizeof(LcApp) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const LcApp *back = reinterpret_cast<const LcApp *>(c->lc.h.data());
+    for (int i = 0; i < n; ++i)
+        if (back[i].status) return fail(c, "loopdb_append: a vector cannot be normalised (BAD_VECTOR): row %d", i);
+    hipLaunchKernelGGL(k_lc_append, dim3(n), dim3(64), 0, c->stream, c->lc.S, d_apps, d_vecs, 1);        // all can: write the rows
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    lc_host_appended(c->lc.H, n, apps.data());
+    return 0;
+}
+
+int svslam_loop_candidates_batch(svslam_ctx *c, int njobs, svslam_lc_job *jobs, const svslam_lc_params *prm, const float *vecs)
+{
+    if (!c) return -1;
+    if (njobs < 0) return fail(c, "loop_candidates: negative count");
+    if (!prm) return fail(c, "loop_candidates: null params");
+    if (njobs && (!jobs || !vecs)) return fail(c, "loop_candidates: null array");
+    if (arena_busy(c)) return -1;
+    const LcParams P = { prm->weak, prm->strong, prm->max_num_weak, prm->min_gap };
+    std::vector<int> streams((size_t)njobs), kfs((size_t)njobs);
+    for (int j = 0; j < njobs; ++j) { streams[(size_t)j] = jobs[j].stream; kfs[(size_t)j] = jobs[j].kf_id; }
+    std::vector<LcJob> J((size_t)njobs);
+    const char *why = lc_check_jobs(c->lc.H, njobs, streams.data(), kfs.data(), P, J.data());
+    if (why) return fail(c, "loop_candidates: %s", why);
+    if (njobs == 0) return 0;
+    const size_t head = lc_head(sizeof(LcJob) * (size_t)njobs), vbytes = sizeof(float) * (size_t)njobs * c->lc.S.dim;
+    if (lc_stage(c, head + vbytes, "loop_candidates")) return -1;
+    memcpy(c->lc.h.data(), J.data(), sizeof(LcJob) * (size_t)njobs);
+    memcpy(c->lc.h.data() + head, vecs, vbytes);
+    HIPCHK(c, hipMemcpyAsync(c->lc.d, c->lc.h.data(), head + vbytes, hipMemcpyHostToDevice, c->stream));
+    tm_begin(c, FAM_LC, 0);                                     // the units are known once the jobs are back
+    hipLaunchKernelGGL(k_lc_candidates, dim3(njobs), dim3(LC_THREADS), 0, c->stream, c->lc.S, P, reinterpret_cast<LcJob *>(c->lc.d),
+                       reinterpret_cast<const float *>(c->lc.d + head));
+    tm_end(c);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->lc.h.data(), c->lc.d, sizeof(LcJob) * (size_t)njobs, hipMemcpyDeviceToHost, c->stream));
+    if (d2h_sync(c, 0, 0)) return -1;
+    const LcJob *R = reinterpret_cast<const LcJob *>(c->lc.h.data());
+    long long compared = 0;
+    for (int j = 0; j < njobs; ++j) {
+        jobs[j].status = R[j].status; jobs[j].cand_kf = R[j].cand_kf; jobs[j].best_kf = R[j].best_kf; jobs[j].n_weak = R[j].n_weak;
+        jobs[j].n_compared = R[j].n_compared; jobs[j].best_sim = R[j].best_sim;
+        compared += R[j].n_compared;
+    }
+    if (c->timing) c->tm.units[FAM_LC] += compared;
+    return 0;
+}
+
+int svslam_loopdb_count(svslam_ctx *c, int stream, int *count)
+{
+    if (!c) return -1;
+    if (!count) return fail(c, "loopdb_count: null output");
+    if (c->lc.H.nstreams == 0) return fail(c, "loopdb_count: the store is not configured");
+    if (stream < 0 || stream >= c->lc.H.nstreams) return fail(c, "loopdb_count: unknown stream");
+    *count = c->lc.H.count[(size_t)stream];
+    return 0;
+}
+
+int svslam_loopdb_read(svslam_ctx *c, int stream, int max_rows, int *kf_ids, float *vecs)
+{
+    if (!c) return -1;
+    if (c->lc.H.nstreams == 0) return fail(c, "loopdb_read: the store is not configured");
+    if (stream < 0 || stream >= c->lc.H.nstreams) return fail(c, "loopdb_read: unknown stream");
+    if (max_rows < 0) return fail(c, "loopdb_read: negative count");
+    const int n = c->lc.H.count[(size_t)stream] < max_rows ? c->lc.H.count[(size_t)stream] : max_rows;
+    if (n == 0) return 0;
+    if (!kf_ids || !vecs) return fail(c, "loopdb_read: null array");
+    const LcStore &S = c->lc.S;
+    std::vector<float> rows;
+    try { rows.resize((size_t)n * S.dp); }
+    catch (const std::bad_alloc &) { return fail(c, "loopdb_read: no host memory"); }
+    const size_t at = (size_t)stream * S.capacity;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(rows.data(), S.rows + at * S.dp, sizeof(float) * (size_t)n * S.dp, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(kf_ids, S.ids + at, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+    for (int r = 0; r < n; ++r) lc_unpermute(rows.data() + (size_t)r * S.dp, S.dim, S.dp, vecs + (size_t)r * S.dim);
     return 0;
 }
 

@@ -122,6 +122,12 @@ public:
     int brief_describe(int n, svslam_brief_job *jobs, const svslam_brief_params *prm, int total_pts, const float *xy, uint8_t *desc, int *desc_pt)
     { return svslam_brief_describe_batch(ctx_, n, jobs, prm, total_pts, xy, desc, desc_pt); }
 
+    int loopdb_configure(int nstreams, int capacity, int dim) { return svslam_loopdb_configure(ctx_, nstreams, capacity, dim); }
+    int loopdb_append(int n, const int *streams, const int *kf_ids, const float *vecs) { return svslam_loopdb_append_batch(ctx_, n, streams, kf_ids, vecs); }
+    int loop_candidates(int n, svslam_lc_job *jobs, const svslam_lc_params *prm, const float *vecs) { return svslam_loop_candidates_batch(ctx_, n, jobs, prm, vecs); }
+    int loopdb_count(int stream, int *count) { return svslam_loopdb_count(ctx_, stream, count); }
+    int loopdb_read(int stream, int max_rows, int *kf_ids, float *vecs) { return svslam_loopdb_read(ctx_, stream, max_rows, kf_ids, vecs); }
+
     int local_ba_submit(int n, const svslam_ba_job *jobs, const double *cam_l, const double *ext_l, const double *cam_r,
                         const double *ext_r, int total_kf, const double *poses, int total_lm, const double *pts,
                         int total_obs, const int *okf, const int *olm, const uint8_t *oright, const float *ouv,

@@ -160,4 +160,70 @@ extern "C" int svs_pipe_verify_loops_stored(void *p, int npairs, const svs_loop_
         return -1;
     }
 }
+// Loop detection (product build only: the CPU twins' providers have no loop_candidates)
+extern "C" int svs_pipe_loopdb_configure(void *p, int capacity, int dim)
+{
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    try {
+        if (!h->pipe->ConfigureLoopStore(capacity, dim)) { g_err = h->pipe->last_error(); return -1; }
+        return 0;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+extern "C" int svs_pipe_detect_loops(void *p, const float *vecs, const svs_loop_detect_params *dp, const void *loop_params, svs_loop_detection *results)
+{
+    typedef svs::Pipeline<SVS_PIPE_KERNELS> Pipe;
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    if (!vecs || !dp || !loop_params || !results) { g_err = "svs_pipe_detect_loops: null argument"; return -1; }
+    try {
+        Pipe::LoopDetectParams P;
+        P.cand.weak = dp->weak; P.cand.strong = dp->strong; P.cand.max_num_weak = dp->max_num_weak; P.cand.min_gap = dp->min_gap;
+        P.verify = *static_cast<const svslam_loop_params *>(loop_params);
+        P.keyframes_to_ignore_after_loop = dp->keyframes_to_ignore_after_loop;
+        std::vector<Pipe::LoopDetection> ds;
+        if (!h->pipe->DetectLoops(vecs, P, &ds)) { g_err = h->pipe->last_error(); return -1; }
+        for (size_t s = 0; s < ds.size(); ++s) {
+            const Pipe::LoopDetection &D = ds[s];
+            svs_loop_detection &o = results[s];
+            std::memset(&o, 0, sizeof(o));
+            o.is_keyframe = D.is_keyframe; o.skipped = D.skipped; o.searched = D.searched; o.verified = D.verified; o.stored = D.stored;
+            o.kf_id = D.kf_id;
+            o.cand_status = D.searched ? D.cand.status : -1; o.cand_kf = D.searched ? D.cand.cand_kf : -1; o.best_kf = D.searched ? D.cand.best_kf : -1;
+            o.n_weak = D.cand.n_weak; o.n_compared = D.cand.n_compared; o.best_sim = D.cand.best_sim;
+            const Pipe::LoopResult &R = D.loop;
+            o.loop.status = D.verified ? R.status : -1; o.loop.n_matches = R.n_matches; o.loop.n_points = R.n_points; o.loop.n_inliers = R.n_inliers;
+            o.loop.need_correction = R.need_correction ? 1 : 0;
+            std::memcpy(o.loop.T_corr, R.T_corr.v, 56); std::memcpy(o.loop.T_rel, R.T_rel.v, 56); o.loop.d = R.d;
+        }
+        return 0;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+extern "C" long long svs_pipe_loop_matches(void *p, int stream, int *match4, long long cap)
+{
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    const auto &ds = h->pipe->LastDetections();
+    if (stream < 0 || (size_t)stream >= ds.size() || !ds[(size_t)stream].verified) { g_err = "svs_pipe_loop_matches: the last svs_pipe_detect_loops verified nothing on this stream"; return -1; }
+    const auto &R = ds[(size_t)stream].loop;
+    const long long n = R.n_matches;
+    if (match4 && cap >= n)
+        for (long long k = 0; k < n; ++k) { match4[4 * k] = R.match_c[(size_t)k]; match4[4 * k + 1] = R.match_q[(size_t)k]; match4[4 * k + 2] = R.match_dist[(size_t)k]; match4[4 * k + 3] = R.match_inlier[(size_t)k]; }
+    return n;
+}
+extern "C" long long svs_pipe_loopdb_ids(void *p, int stream, int *ids, long long cap)
+{
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    int n = 0;
+    if (h->kernels->loopdb_count(stream, &n) != 0) { g_err = h->kernels->last_error(); return -1; }
+    if (ids && cap >= n && n) {
+        std::vector<float> rows((size_t)n * 4096);
+        if (h->kernels->loopdb_read(stream, n, ids, rows.data()) != 0) { g_err = h->kernels->last_error(); return -1; }
+    }
+    return n;
+}
+extern "C" long long svs_pipe_last_closed_keyframe(void *p, int stream) { return static_cast<PipeHandle *>(p)->pipe->LastClosedKeyframe(stream); }
 extern "C" void *svs_pipe_backend_ctx(void *p) { return static_cast<PipeHandle *>(p)->kernels->backend_ctx(); }

@@ -114,6 +114,33 @@ long long svs_pipe_keyframe_descriptors(void *p, int stream, long long kf_id, ui
 typedef struct svs_loop_pair { int stream; long long kf_id, cand_kf_id; } svs_loop_pair;
 int svs_pipe_verify_loops_stored(void *p, int npairs, const svs_loop_pair *pairs, const void *params, svs_loop_result *results, int *match4_or_null,
                                  long long match_rows);
+/* The store of global image descriptors svs_pipe_detect_loops searches (svslam_loopdb_configure): capacity rows of dim
+ * floats for every stream, emptied; every stream's last closed keyframe is forgotten.  Product library only. */
+int svs_pipe_loopdb_configure(void *p, int capacity, int dim);
+/* LoopClosure::AddNewKeyFrame and one turn of LoopClosurePipeline (src/loopclosure.cpp:182-198, :801-872) for every stream whose last
+ * step made a keyframe, after svs_pipe_describe_new_keyframes: the skip rule after a closed loop, the candidate search
+ * (svslam_loop_candidates_batch, one call), the verification of every FOUND candidate (svs_pipe_verify_loops_stored, one call; an
+ * ACCEPTED pair is a loop edge and the stream's last closed keyframe, and is not stored), the append of every other keyframe (one
+ * call).  vecs: [nstreams][dim] global descriptors, the rows of streams without a new keyframe are not read.  loop_params:
+ * svslam_loop_params (cam and ext_l are filled in by the pipeline).  results: [nstreams]; cand_status and loop.status are -1 where that
+ * stage did not run.  The matches of a verified stream: svs_pipe_loop_matches.  -1 (svs_pipe_last_error, nothing done): device_map =
+ * 1, a store that was not configured, a new keyframe that was never described, a full stream, a kernel's refusal.  LocalFusion is the
+ * caller's. */
+typedef struct svs_loop_detect_params { float weak, strong; int max_num_weak, min_gap; long long keyframes_to_ignore_after_loop; } svs_loop_detect_params;
+typedef struct svs_loop_detection {
+    int is_keyframe, skipped, searched, verified, stored, reserved;
+    long long kf_id;
+    int cand_status, cand_kf, best_kf, n_weak, n_compared; float best_sim;
+    svs_loop_result loop;
+} svs_loop_detection;
+int svs_pipe_detect_loops(void *p, const float *vecs, const svs_loop_detect_params *dp, const void *loop_params, svs_loop_detection *results);
+/* the matches (candidate row, current row, distance, inlier) of the pair the last svs_pipe_detect_loops verified on a stream: returns
+ * their number (nothing written when cap is smaller or match4 is NULL), -1 when it verified none there */
+long long svs_pipe_loop_matches(void *p, int stream, int *match4, long long cap);
+/* the keyframe ids a stream's store holds: returns their number (nothing written when cap is smaller or ids is NULL) */
+long long svs_pipe_loopdb_ids(void *p, int stream, int *ids, long long cap);
+/* the keyframe that last closed a loop on the stream, -1: none */
+long long svs_pipe_last_closed_keyframe(void *p, int stream);
 /* on != 0: keyframes that leave the window from now on keep their feature lists, as the reference's do (svs_pipe_verify_loops
  * reads the candidate keyframe's; a keyframe whose lists were released is refused there).  Off by default. */
 int svs_pipe_keep_keyframe_features(void *p, int on);

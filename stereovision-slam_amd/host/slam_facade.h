@@ -273,6 +273,9 @@ struct FrontendOptions {            // the hyper-parameters Frontend::Frontend()
     // that VerifyLoop(kf, cand, out) needs no descriptors from the caller.  `loop_descriptors: 1` in the YAML (or this field);
     // 0 (default): nothing is described, behaviour and memory as without the key.  Needs the host map (device_map: 0).
     int loop_descriptors = 0;
+    // Frontend::DetectLoop's store of global descriptors: `loop_store_capacity` keyframes of `loop_descriptor_dim` floats (the
+    // reference's vector has 1280); allocated at the first DetectLoop, never without it
+    int loop_store_capacity = 4096, loop_descriptor_dim = 1280;
     static FrontendOptions FromConfig(const ConfigFile &c)
     {
         FrontendOptions o;
@@ -280,6 +283,8 @@ struct FrontendOptions {            // the hyper-parameters Frontend::Frontend()
         o.low_latency = (int)c.Num("low_latency", o.low_latency);
         o.pose_xtol = c.Num("pose_xtol", o.pose_xtol);
         o.loop_descriptors = (int)c.Num("loop_descriptors", o.loop_descriptors);
+        o.loop_store_capacity = (int)c.Num("loop_store_capacity", o.loop_store_capacity);
+        o.loop_descriptor_dim = (int)c.Num("loop_descriptor_dim", o.loop_descriptor_dim);
         o.num_features = (int)c.Num("num_features", o.num_features);
         o.num_features_init = (int)c.Num("num_features_init", o.num_features_init);
         o.num_features_tracking = (int)c.Num("num_features_tracking", o.num_features_tracking);
@@ -377,6 +382,24 @@ public:
         if (out) *out = res[0];
         return true;
     }
+    // LoopClosure::AddNewKeyFrame and one turn of LoopClosurePipeline (src/loopclosure.cpp:182-198, :801-872) for the keyframe the
+    // last AddFrame made: Pipeline::DetectLoops on stream 0 with the caller's global descriptor of `loop_descriptor_dim` floats
+    // (the reference's MobileNetV2 vector; the network is not part of this project).  The store is configured at the first call:
+    // `loop_store_capacity` keyframes (default 4096).  Needs `loop_descriptors: 1`.  out->is_keyframe is false when the last frame
+    // made no keyframe or it was handled already.  LocalFusion stays the caller's: out->loop carries what it needs.
+    bool DetectLoop(const float *vec, const typename Pipeline<K>::LoopDetectParams &params, typename Pipeline<K>::LoopDetection *out)
+    {
+        if (!pipe_) return false;
+        if (!opt_.loop_descriptors) throw SLAMException("DetectLoop needs loop_descriptors: 1 in the configuration");
+        if (!loop_store_ready_) {
+            if (!pipe_->ConfigureLoopStore(opt_.loop_store_capacity, opt_.loop_descriptor_dim)) return false;
+            loop_store_ready_ = true;
+        }
+        std::vector<typename Pipeline<K>::LoopDetection> res;
+        if (!pipe_->DetectLoops(vec, params, &res)) return false;
+        if (out) *out = res[0];
+        return true;
+    }
     K *kernels() { return kernels_.get(); }
     bool LowLatency() const { return opt_.low_latency != 0; }
 
@@ -466,6 +489,7 @@ private:
     std::function<void(const Frame::Ptr &)> loopclosure_, viewer_;
     std::unique_ptr<K> kernels_;
     std::unique_ptr<Pipeline<K>> pipe_;
+    bool loop_store_ready_ = false;
     int src_w_ = 0, src_h_ = 0;
 };
 
@@ -599,6 +623,20 @@ public:
     bool VerifyLoop(unsigned long kf_id, unsigned long cand_kf_id, typename Pipeline<K>::LoopResult *out, unsigned seed = 0)
     {
         return frontend_->VerifyLoop(kf_id, cand_kf_id, loop_params(seed), out);
+    }
+    // Frontend::DetectLoop with the thresholds of the configuration file, in the reference's spelling (src/loopclosure.cpp:26-36):
+    // potential_loop_weak_threshold, potential_loop_strong_threshold, max_num_weak_threshold, keyframes_to_ignore_after_loop, the
+    // keys of loop_params; the gap of 20 keyframes is :244's literal unless `loop_min_keyframe_gap` (a key of this project) says otherwise.  Call it after an AddFrame that made a keyframe.
+    bool DetectLoop(const float *vec, typename Pipeline<K>::LoopDetection *out, unsigned seed = 0)
+    {
+        typename Pipeline<K>::LoopDetectParams p;
+        p.cand.weak = (float)config_.Num("potential_loop_weak_threshold", 0.93);
+        p.cand.strong = (float)config_.Num("potential_loop_strong_threshold", 0.95);
+        p.cand.max_num_weak = (int)config_.Num("max_num_weak_threshold", 3);
+        p.cand.min_gap = (int)config_.Num("loop_min_keyframe_gap", 20);
+        p.verify = loop_params(seed);
+        p.keyframes_to_ignore_after_loop = (long)config_.Num("keyframes_to_ignore_after_loop", 5);
+        return frontend_->DetectLoop(vec, p, out);
     }
     FrontendStatus GetFrontendStatus() const { return frontend_->GetStatus(); }
     // keyframes.txt + landmarks.pcd under output_dir (:198-310; the reference adds a time-stamped folder)

@@ -100,6 +100,7 @@ struct Frame {
     std::vector<uint8_t> desc;
     std::vector<int> desc_feat_indx;
     bool described = false;
+    bool loop_checked = false;        // Pipeline::DetectLoops has handled this keyframe (skipped, searched, stored or not)
 };
 
 struct ObsRef {
@@ -895,11 +896,110 @@ public:
         }
         return VerifyLoops(qs, params, results);
     }
+    // The store of global image descriptors DetectLoops searches (svslam_loopdb_configure): capacity rows of dim floats
+    // for every stream, emptied.  Every stream's last_closed is forgotten with it.
+    bool ConfigureLoopStore(int capacity, int dim)
+    {
+        Flush();
+        if (k_.loopdb_configure(nstreams(), capacity, dim) != 0) return refuse(std::string("ConfigureLoopStore: ") + k_.last_error());
+        lc_dim_ = dim; lc_capacity_ = capacity;
+        lc_last_closed_.assign((size_t)nstreams(), -1);
+        return true;
+    }
+    // LoopClosure::AddNewKeyFrame (src/loopclosure.cpp:182-198) and one turn of LoopClosurePipeline (:801-872) for every stream whose
+    // last step made a keyframe, synchronously, after DescribeNewKeyframes.  vecs holds one global descriptor of dim floats per
+    // stream, [nstreams][dim]; the rows of streams without a new keyframe are not read.
+    //   1. kf_id - last_closed <= keyframes_to_ignore_after_loop: skipped, never stored (:191-196)
+    //   2. ONE loop_candidates call for all remaining streams (LoopKeyframeCandidate, :227-284)
+    //   3. ONE VerifyLoopsStored call for the jobs that came back FOUND (:835-840)
+    //   4. an ACCEPTED pair is a loop edge already (VerifyLoops records it); it sets the stream's last_closed and is NOT stored (:861, :868)
+    //   5. every other keyframe is appended to the store, in one call (:870)
+    // A keyframe whose vector cannot be normalised (BAD_VECTOR) is not stored either; the reference would store NaNs.  LocalFusion
+    // (:858) is not done: the result carries the LoopResult for it.  A keyframe is handled once: a second call after the same step
+    // finds nothing to do.  False (last_error(), nothing done): device_map = 1, a store that was not configured, a new keyframe
+    // that was never described, a stream whose store is full, the provider's refusal.
+    struct LoopDetectParams { svslam_lc_params cand; svslam_loop_params verify; long keyframes_to_ignore_after_loop; };
+    struct LoopDetection {
+        bool is_keyframe = false, skipped = false, searched = false, verified = false, stored = false;
+        long kf_id = -1;
+        svslam_lc_job cand = {};          // status, cand_kf, best_sim, best_kf, n_weak, n_compared when searched
+        LoopResult loop;                  // when verified
+    };
+    bool DetectLoops(const float *vecs, const LoopDetectParams &params, std::vector<LoopDetection> *results)
+    {
+        if (device_map()) return refuse("DetectLoops: with device_map = 1 the keyframes' features live on the device; not supported yet");
+        if (lc_dim_ == 0) return refuse("DetectLoops: the store was not configured (ConfigureLoopStore)");
+        if (!vecs) return refuse("DetectLoops: null descriptors");
+        const int ns = nstreams();
+        std::vector<LoopDetection> out((size_t)ns);
+        std::vector<Frame *> fresh((size_t)ns, nullptr);
+        for (int s = 0; s < ns; ++s) {
+            Frame *f = streams_[s]->last;
+            if (!f || !f->is_keyframe || f->loop_checked) continue;
+            if (!f->described) return refuse("DetectLoops: the new keyframe was never described (DescribeNewKeyframes after its step)");
+            int count = 0;
+            if (k_.loopdb_count(s, &count) != 0) return refuse(std::string("DetectLoops: ") + k_.last_error());
+            if (count >= lc_capacity_) return refuse("DetectLoops: the stream's store is full");
+            fresh[(size_t)s] = f;
+        }
+        Flush();
+        std::vector<svslam_lc_job> jobs;
+        std::vector<float> q;
+        for (int s = 0; s < ns; ++s) {
+            Frame *f = fresh[(size_t)s];
+            if (!f) continue;
+            LoopDetection &D = out[(size_t)s];
+            D.is_keyframe = true; D.kf_id = f->keyframe_id;
+            const long closed = lc_last_closed_[(size_t)s];
+            if (closed >= 0 && f->keyframe_id - closed <= params.keyframes_to_ignore_after_loop) { D.skipped = true; continue; }
+            svslam_lc_job J;
+            std::memset(&J, 0, sizeof(J));
+            J.stream = s; J.kf_id = (int)f->keyframe_id;
+            jobs.push_back(J);
+            q.insert(q.end(), vecs + (size_t)s * lc_dim_, vecs + ((size_t)s + 1) * lc_dim_);
+        }
+        if (!jobs.empty() && k_.loop_candidates((int)jobs.size(), jobs.data(), &params.cand, q.data()) != 0)
+            return refuse(std::string("DetectLoops: ") + k_.last_error());
+        std::vector<LoopPair> pairs;
+        for (const svslam_lc_job &J : jobs) {
+            out[(size_t)J.stream].searched = true; out[(size_t)J.stream].cand = J;
+            if (J.status == SVSLAM_LC_FOUND) pairs.push_back(LoopPair{ J.stream, (long)J.kf_id, (long)J.cand_kf });
+        }
+        std::vector<LoopResult> rs;
+        if (!pairs.empty() && !VerifyLoopsStored(pairs, params.verify, &rs)) return false;
+        for (size_t i = 0; i < pairs.size(); ++i) {
+            LoopDetection &D = out[(size_t)pairs[i].stream];
+            D.verified = true; D.loop = std::move(rs[i]);
+            if (D.loop.status == SVSLAM_LOOP_ACCEPTED) lc_last_closed_[(size_t)pairs[i].stream] = pairs[i].kf_id;
+        }
+        std::vector<int> as, ak;
+        std::vector<float> av;
+        for (size_t j = 0; j < jobs.size(); ++j) {
+            const LoopDetection &D = out[(size_t)jobs[j].stream];
+            if (jobs[j].status == SVSLAM_LC_BAD_VECTOR || (D.verified && D.loop.status == SVSLAM_LOOP_ACCEPTED)) continue;
+            as.push_back(jobs[j].stream); ak.push_back(jobs[j].kf_id);
+            av.insert(av.end(), q.begin() + (long)(j * (size_t)lc_dim_), q.begin() + (long)((j + 1) * (size_t)lc_dim_));
+        }
+        if (!as.empty() && k_.loopdb_append((int)as.size(), as.data(), ak.data(), av.data()) != 0)
+            return refuse(std::string("DetectLoops: ") + k_.last_error());
+        for (int s : as) out[(size_t)s].stored = true;
+        for (int s = 0; s < ns; ++s) if (fresh[(size_t)s]) fresh[(size_t)s]->loop_checked = true;
+        last_detections_ = out;
+        if (results) *results = std::move(out);
+        return true;
+    }
+    // what the last DetectLoops call returned (the C API reads a stream's matches from here)
+    const std::vector<LoopDetection> &LastDetections() const { return last_detections_; }
+    long LastClosedKeyframe(int s) const { return s >= 0 && (size_t)s < lc_last_closed_.size() ? lc_last_closed_[(size_t)s] : -1; }
     const std::string &last_error() const { return refusal_; }
 
 private:
     bool refuse(const std::string &why) { refusal_ = why; return false; }
     std::string refusal_;
+    // DetectLoops: the store's shape (0: not configured), the keyframe that last closed a loop per stream (-1: none), the last results
+    int lc_dim_ = 0, lc_capacity_ = 0;
+    std::vector<long> lc_last_closed_;
+    std::vector<LoopDetection> last_detections_;
     void check(int rc, const char *what)
     {
         if (rc != 0) throw std::runtime_error(std::string(what) + " failed: " + k_.last_error());

@@ -97,6 +97,17 @@ class LoopPair(C.Structure):
     _fields_ = [("stream", C.c_int), ("kf_id", C.c_longlong), ("cand_kf_id", C.c_longlong)]
 
 
+class LoopDetectParams(C.Structure):
+    _fields_ = [("weak", C.c_float), ("strong", C.c_float), ("max_num_weak", C.c_int), ("min_gap", C.c_int),
+                ("keyframes_to_ignore_after_loop", C.c_longlong)]
+
+
+class LoopDetection(C.Structure):
+    _fields_ = [("is_keyframe", C.c_int), ("skipped", C.c_int), ("searched", C.c_int), ("verified", C.c_int), ("stored", C.c_int),
+                ("reserved", C.c_int), ("kf_id", C.c_longlong), ("cand_status", C.c_int), ("cand_kf", C.c_int), ("best_kf", C.c_int),
+                ("n_weak", C.c_int), ("n_compared", C.c_int), ("best_sim", C.c_float), ("loop", LoopResult)]
+
+
 def _bind(L):
     L.svs_pipe_create.restype = C.c_void_p
     L.svs_pipe_create.argtypes = [C.POINTER(PipeConfig), C.c_int, C.c_int]
@@ -129,6 +140,15 @@ def _bind(L):
         L.svs_pipe_keyframe_descriptors.restype = C.c_longlong
         L.svs_pipe_keyframe_descriptors.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong]
         L.svs_pipe_verify_loops_stored.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
+    if hasattr(L, "svs_pipe_detect_loops"):
+        L.svs_pipe_loopdb_configure.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.svs_pipe_detect_loops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.svs_pipe_loop_matches.restype = C.c_longlong
+        L.svs_pipe_loop_matches.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
+        L.svs_pipe_loopdb_ids.restype = C.c_longlong
+        L.svs_pipe_loopdb_ids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
+        L.svs_pipe_last_closed_keyframe.restype = C.c_longlong
+        L.svs_pipe_last_closed_keyframe.argtypes = [C.c_void_p, C.c_int]
     return L
 
 
@@ -347,6 +367,67 @@ class Pipeline:
                             matches=m4[row:row + r.n_matches].astype(np.int64)))
             row += rows_of[i]
         return out
+
+    def loopdb_configure(self, capacity, dim=1280):
+        """the store of global image descriptors detect_loops searches (svs_pipe_loopdb_configure): capacity rows of dim floats per stream"""
+        if self.L.svs_pipe_loopdb_configure(self.h, int(capacity), int(dim)) != 0:
+            raise RuntimeError("svs_pipe_loopdb_configure refused: " + self.L.svs_pipe_last_error().decode())
+        self._lc_dim = int(dim)
+
+    def detect_loops(self, vecs, keyframes_to_ignore_after_loop=5, weak=None, strong=None, max_num_weak=None, min_gap=None, **loop_params):
+        """LoopClosure::AddNewKeyFrame + one turn of LoopClosurePipeline for every stream whose last step made a keyframe
+        (svs_pipe_detect_loops), after describe_new_keyframes: skip rule, candidate search, verification, loop edge, store update.
+        vecs: [nstreams, dim] global descriptors (rows of streams without a new keyframe are not read).  weak, strong, max_num_weak,
+        min_gap: LC_DEFAULTS; loop_params: as verify_loops.  Returns one dict per stream: is_keyframe, skipped, searched, verified,
+        stored, kf_id, cand (status, cand_kf, best_sim, best_kf, n_weak, n_compared) or None, loop (as verify_loops) or None."""
+        import importlib
+        _svs = importlib.import_module(__package__)
+        unknown = set(loop_params) - set(_svs.LOOP_DEFAULTS)
+        if unknown:
+            raise TypeError("detect_loops: unknown parameter(s) %s" % sorted(unknown))
+        p = dict(_svs.LOOP_DEFAULTS); p.update(loop_params)
+        c = dict(_svs.LC_DEFAULTS)
+        c.update({k: v for k, v in dict(weak=weak, strong=strong, max_num_weak=max_num_weak, min_gap=min_gap).items() if v is not None})
+        ns = self.n
+        v = np.ascontiguousarray(vecs, np.float32).reshape(ns, getattr(self, "_lc_dim", -1))     # unconfigured: the library refuses
+        D = LoopDetectParams(float(c["weak"]), float(c["strong"]), int(c["max_num_weak"]), int(c["min_gap"]), int(keyframes_to_ignore_after_loop))
+        P = _svs.LoopParams((C.c_double * 4)(), (C.c_double * 7)(), int(p["min_matches"]), int(p["ransac_iters"]), float(p["reproj_px"]),
+                            float(p["max_pose_distance"]), float(p["min_pose_difference"]), float(p["max_pose_difference"]),
+                            int(p["seed"]) & 0xFFFFFFFF, 0)
+        res = (LoopDetection * ns)()
+        if self.L.svs_pipe_detect_loops(self.h, v.ctypes.data_as(C.c_void_p), C.byref(D), C.byref(P), res) != 0:
+            raise RuntimeError("svs_pipe_detect_loops refused: " + self.L.svs_pipe_last_error().decode())
+        out = []
+        for s in range(ns):
+            r = res[s]
+            d = dict(is_keyframe=bool(r.is_keyframe), skipped=bool(r.skipped), searched=bool(r.searched), verified=bool(r.verified),
+                     stored=bool(r.stored), kf_id=r.kf_id, cand=None, loop=None)
+            if r.searched:
+                d["cand"] = dict(status=r.cand_status, cand_kf=r.cand_kf, best_sim=np.float32(r.best_sim), best_kf=r.best_kf, n_weak=r.n_weak,
+                                 n_compared=r.n_compared)
+            if r.verified:
+                l = r.loop
+                m4 = np.zeros((max(l.n_matches, 1), 4), np.int32)
+                if self.L.svs_pipe_loop_matches(self.h, s, m4.ctypes.data_as(C.c_void_p), l.n_matches) != l.n_matches:
+                    raise RuntimeError("svs_pipe_loop_matches: " + self.L.svs_pipe_last_error().decode())
+                d["loop"] = dict(status=l.status, n_matches=l.n_matches, n_points=l.n_points, n_inliers=l.n_inliers,
+                                 need_correction=bool(l.need_correction), T_corr=np.array(l.T_corr), T_rel=np.array(l.T_rel), d=l.d,
+                                 matches=m4[:l.n_matches].astype(np.int64))
+            out.append(d)
+        return out
+
+    def loopdb_ids(self, stream):
+        """the keyframe ids a stream's store holds (svs_pipe_loopdb_ids)"""
+        n = self.L.svs_pipe_loopdb_ids(self.h, int(stream), None, 0)
+        if n < 0:
+            raise RuntimeError("svs_pipe_loopdb_ids refused: " + self.L.svs_pipe_last_error().decode())
+        ids = np.zeros(n, np.int32)
+        if n and self.L.svs_pipe_loopdb_ids(self.h, int(stream), ids.ctypes.data_as(C.c_void_p), n) != n:
+            raise RuntimeError("svs_pipe_loopdb_ids refused: " + self.L.svs_pipe_last_error().decode())
+        return ids
+
+    def last_closed_keyframe(self, stream):
+        return self.L.svs_pipe_last_closed_keyframe(self.h, int(stream))
 
     def map_snapshot(self, stream=0):
         """the host map of one stream after the last step (svs_pipe_map_snapshot): active keyframe ids and poses, active landmarks

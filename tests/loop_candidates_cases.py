@@ -1,0 +1,473 @@
+"""The cases of the loop candidate search, shared by the host-emulation tests, the device tests and the mutants.  A case is a script of
+calls (configure, append, candidates, read, count); it runs once over tests/ref_loop_candidates.py and once over the implementation, and
+everything both returned is compared EXACTLY: refusal or not, every status, id and count, the bits of every similarity and of every stored
+row.  No tolerance appears.
+
+The boundaries the cases sit on: dim 1, 63, 64, 65 (the 64 accumulators), 128, 1280, 4096 and 255 / 256 / 257 (the row layout's chunk of
+256); 0 .. 600 stored rows with 3 / 4 / 5 (the four rows a wave reduces per pass) and 15 / 16 / 17 (the sixteen rows the four waves take
+per group); the gap by id at kf_id - 21 / - 20 / - 19; ties inside a wave and across waves; each strict compare at its own bits."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+import ref_loop_candidates as rl
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU = os.path.join("tests", "cpp", "lc_host_emu", "emu.cpp")
+SENTINEL = 0x5A5A5A5A
+f32 = np.float32
+
+
+class Job(C.Structure):         # svslam_lc_job
+    _fields_ = [("stream", C.c_int), ("kf_id", C.c_int), ("status", C.c_int), ("cand_kf", C.c_int), ("best_kf", C.c_int),
+                ("n_weak", C.c_int), ("n_compared", C.c_int), ("best_sim", C.c_float)]
+
+
+class Params(C.Structure):      # svslam_lc_params
+    _fields_ = [("weak", C.c_float), ("strong", C.c_float), ("max_num_weak", C.c_int), ("min_gap", C.c_int)]
+
+
+def bits(x):
+    return int(np.array(x, f32).view(np.uint32))
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _result(t):
+    st, cand, sim, bk, nw, nc = t
+    return (int(st), int(cand), bits(sim), int(bk), int(nw), int(nc))
+
+
+# ---- the three drivers: every call returns (reason or None, payload) -----------------------------------------------------------------
+class RefDriver:
+    def __init__(self):
+        self.S = rl.Store()
+
+    def unconfigured(self):
+        return RefDriver()
+
+    def configure(self, ns, cap, dim):
+        return self.S.configure(ns, cap, dim)
+
+    def append(self, streams, ids, vecs):
+        return self.S.append(list(streams), list(ids), vecs)
+
+    def candidates(self, jobs, vecs, **prm):
+        r = self.S.candidates(list(jobs), vecs, **dict(rl.DEFAULTS, **prm))
+        return (r, None) if isinstance(r, str) else (None, [_result(t) for t in r])
+
+    def read(self, stream):
+        return self.S.read(stream)
+
+    def count(self, stream):
+        return self.S.count(stream)
+
+
+class _Native:
+    """what the host emulation and the C ABI have in common: the job array with marked outputs, and that a refusal leaves them marked"""
+
+    def _jobs(self, jobs):
+        arr = (Job * max(len(jobs), 1))()
+        for i, (s, k) in enumerate(jobs):
+            arr[i].stream, arr[i].kf_id = int(s), int(k)
+            for f in ("status", "cand_kf", "best_kf", "n_weak", "n_compared"):
+                setattr(arr[i], f, SENTINEL)
+            arr[i].best_sim = -7.5
+        return arr
+
+    def _out(self, rc, arr, n):
+        if rc != 0:
+            for i in range(n):
+                assert (arr[i].status, arr[i].cand_kf, arr[i].best_kf, arr[i].n_weak, arr[i].n_compared, arr[i].best_sim) == \
+                    (SENTINEL,) * 5 + (-7.5,), "a refused call wrote into job %d" % i
+            return self.error(), None
+        return None, [(arr[i].status, arr[i].cand_kf, bits(arr[i].best_sim), arr[i].best_kf, arr[i].n_weak, arr[i].n_compared) for i in range(n)]
+
+    @staticmethod
+    def _prm(prm):
+        p = dict(rl.DEFAULTS, **prm)
+        return Params(p["weak"], p["strong"], p["max_num_weak"], p["min_gap"])
+
+
+class EmuDriver(_Native):
+    def __init__(self, lib):
+        self.L = lib
+        lib.emu_lc_error.restype = C.c_char_p
+        self.dim = 0
+
+    def error(self):
+        return self.L.emu_lc_error().decode()
+
+    def unconfigured(self):
+        self.L.emu_lc_configure(1, 1, 1)
+        self.L.emu_lc_reset()
+        return self
+
+    def configure(self, ns, cap, dim):
+        if self.L.emu_lc_configure(ns, cap, dim) != 0:
+            return self.error()
+        self.dim, self.cap = dim, cap
+        return None
+
+    def append(self, streams, ids, vecs):
+        s = np.ascontiguousarray(streams, np.int32); k = np.ascontiguousarray(ids, np.int32); v = np.ascontiguousarray(vecs, f32)
+        return None if self.L.emu_lc_append(len(s), _ptr(s), _ptr(k), _ptr(v)) == 0 else self.error()
+
+    def candidates(self, jobs, vecs, **prm):
+        arr = self._jobs(jobs); v = np.ascontiguousarray(vecs, f32); P = self._prm(prm)
+        return self._out(self.L.emu_lc_candidates(len(jobs), arr, C.byref(P), _ptr(v)), arr, len(jobs))
+
+    def count(self, stream):
+        return self.L.emu_lc_count(stream)
+
+    def read(self, stream):
+        n = self.count(stream)
+        ids = np.zeros(n, np.int32); rows = np.zeros((n, self.dim), f32)
+        assert self.L.emu_lc_read(stream, n, _ptr(ids), _ptr(rows)) == 0
+        return ids, rows
+
+
+class AbiDriver(_Native):
+    """the C ABI of the library on the device, through a Context's handle"""
+
+    def __init__(self, svs, ctx=None):
+        self.svs = svs
+        self.ctx = ctx if ctx is not None else svs.Context(64, 48, max_slots=1, max_jobs=1)
+        self.L, self.h = self.ctx.L, self.ctx.h
+        self.dim = 0
+        self.fresh = []
+
+    def error(self):
+        return self.L.svslam_last_error(self.h).decode()
+
+    def unconfigured(self):
+        self.fresh.append(AbiDriver(self.svs))          # a context that was never configured: a new one
+        return self.fresh[-1]
+
+    def close(self):
+        for d in self.fresh:
+            d.close()
+        self.ctx.close()
+
+    def configure(self, ns, cap, dim):
+        if self.L.svslam_loopdb_configure(self.h, ns, cap, dim) != 0:
+            return self.error()
+        self.dim = dim
+        return None
+
+    def append(self, streams, ids, vecs):
+        s = np.ascontiguousarray(streams, np.int32); k = np.ascontiguousarray(ids, np.int32); v = np.ascontiguousarray(vecs, f32)
+        return None if self.L.svslam_loopdb_append_batch(self.h, len(s), _ptr(s), _ptr(k), _ptr(v)) == 0 else self.error()
+
+    def candidates(self, jobs, vecs, **prm):
+        arr = self._jobs(jobs); v = np.ascontiguousarray(vecs, f32); P = self._prm(prm)
+        return self._out(self.L.svslam_loop_candidates_batch(self.h, len(jobs), arr, C.byref(P), _ptr(v)), arr, len(jobs))
+
+    def count(self, stream):
+        n = C.c_int(-1)
+        assert self.L.svslam_loopdb_count(self.h, stream, C.byref(n)) == 0
+        return n.value
+
+    def read(self, stream):
+        n = self.count(stream)
+        ids = np.zeros(n, np.int32); rows = np.zeros((n, self.dim), f32)
+        assert self.L.svslam_loopdb_read(self.h, stream, n, _ptr(ids), _ptr(rows)) == 0
+        return ids, rows
+
+
+def emu_build(src_root, out_dir, opt="-O2"):
+    so = os.path.join(str(out_dir), "liblc_host_emu.so")
+    subprocess.check_call(["g++", opt, "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(str(src_root), EMU), "-o", so])
+    return C.CDLL(so)
+
+
+# ---- a log of everything a script saw ------------------------------------------------------------------------------------------------
+class Log:
+    def __init__(self, drv):
+        self.d, self.seen = drv, []
+
+    def configure(self, *a):
+        e = self.d.configure(*a); self.seen.append(("configure", a, e is None)); return e
+
+    def append(self, streams, ids, vecs):
+        e = self.d.append(streams, ids, vecs); self.seen.append(("append", tuple(ids), e is None)); return e
+
+    def candidates(self, jobs, vecs, **prm):
+        e, r = self.d.candidates(jobs, vecs, **prm); self.seen.append(("candidates", tuple(jobs), e is None, r)); return e, r
+
+    def read(self, streams):
+        for s in streams:
+            ids, rows = self.d.read(s)
+            self.seen.append(("read", s, self.d.count(s), ids.tolist(), rows.view(np.uint32).tolist()))
+
+    def unconfigured(self):
+        self.d = self.d.unconfigured(); self.seen.append(("fresh",))
+
+
+def vecs(seed, n, dim):
+    return np.random.default_rng(seed).standard_normal((n, dim)).astype(f32)
+
+
+def near(v, seed, eps):
+    return (v + f32(eps) * np.random.default_rng(seed).standard_normal(v.shape)).astype(f32)
+
+
+def _ref_result(setup, jobs, q, **prm):
+    """what the reference answers after `setup`: the scripts read their thresholds off it"""
+    d = RefDriver(); setup(d)
+    e, r = d.candidates(jobs, q, **prm)
+    assert e is None
+    return r
+
+
+# ---- the scripts ---------------------------------------------------------------------------------------------------------------------
+def _dim_case(dim):
+    def run(L):
+        L.configure(2, 8, dim)
+        a = vecs(dim, 6, dim); b = vecs(dim + 1, 3, dim)
+        L.append([0] * 6, [0, 3, 4, 9, 10, 12], a)
+        L.append([1] * 3, [1, 2, 5], b)
+        q = np.stack([near(a[2], 7, 0.05), near(b[0], 8, 0.05)])
+        for gap in (0, 2, 20):
+            L.candidates([(0, 13), (1, 13)], q, min_gap=gap, weak=0.5, strong=0.6)
+        L.candidates([(0, 30), (1, 30)], q)
+        L.read([0, 1])
+    return run
+
+
+def _rows_case(n, dim=128):
+    def run(L):
+        L.configure(1, max(n, 1), dim)
+        a = vecs(1000 + n, max(n, 1), dim)[:n]
+        for o in range(0, n, 256):
+            L.append([0] * len(a[o:o + 256]), [3 * i + 1 for i in range(o, min(n, o + 256))], a[o:o + 256])
+        q = near(a[(2 * n) // 3], 5, 0.02) if n else vecs(3, 1, dim)[0]
+        kf = 3 * n + 1
+        L.candidates([(0, kf)], q, min_gap=0)
+        L.candidates([(0, kf)], q, min_gap=0, weak=-1.0, max_num_weak=10 ** 6)       # every row counted
+        L.candidates([(0, kf)], q)
+        L.read([0])
+    return run
+
+
+def _gap_setup(d):
+    d.configure(1, 8, 128)
+    a = vecs(41, 6, 128)
+    a[4] = a[3] * f32(1.5)                  # ids 80 and 81 hold the same direction
+    d.append([0] * 6, [10, 50, 79, 80, 81, 95], a)
+    return a
+
+
+def _gap(L):
+    a = _gap_setup(L)
+    q79, q80 = near(a[2], 1, 0.01), near(a[3], 2, 0.01)
+    for gap in (0, 19, 20, 21, 22):
+        L.candidates([(0, 100)], q80, min_gap=gap, weak=0.5, strong=0.6)
+        L.candidates([(0, 100)], q79, min_gap=gap, weak=0.5, strong=0.6)
+    L.read([0])
+
+
+def _tie_case(places, nrows):
+    def run(L):
+        L.configure(1, nrows, 128)
+        a = vecs(77, nrows, 128)
+        for p in places:
+            a[p] = a[places[0]]
+        L.append([0] * nrows, [2 * i + 5 for i in range(nrows)], a)
+        L.candidates([(0, 1000)], a[places[0]] * f32(3))
+        L.read([0])
+    return run
+
+
+def _nonpositive(L):
+    L.configure(1, 8, 128)
+    q = np.zeros(128, f32); q[:64] = vecs(5, 1, 64)[0]
+    rows = np.zeros((5, 128), f32)
+    rows[0] = -q; rows[1, 64:] = vecs(6, 1, 64)[0]; rows[2] = -2 * q; rows[3, 64:] = 1; rows[4, 100] = -3
+    L.append([0] * 5, [0, 1, 2, 3, 4], rows)
+    L.candidates([(0, 40)], q, weak=-0.5)
+    L.candidates([(0, 40)], q, weak=-0.5, strong=-1.0)      # even a strong threshold below zero finds nothing
+    L.read([0])
+
+
+def _thr_setup(d):
+    d.configure(1, 16, 1280)
+    a = vecs(90, 9, 1280)
+    for i in range(1, 6):
+        a[i] = near(a[0], 90 + i, 0.02 * i)
+    d.append([0] * 9, list(range(9)), a)
+    return a
+
+
+def _strong(L):
+    a = _thr_setup(L)
+    q = near(a[0], 3, 0.01)
+    best = np.array(_ref_result(_thr_setup, [(0, 50)], q)[0][2], np.uint32).view(f32)
+    for s in (best, np.nextafter(best, f32(2)), np.nextafter(best, f32(0))):
+        L.candidates([(0, 50)], q, strong=float(s), weak=0.0, max_num_weak=100)
+
+
+def _weak(L):
+    a = _thr_setup(L)
+    q = near(a[0], 3, 0.01)
+    sims = rl.similarity_rows(rl.normalise(q), np.array([rl.normalise(v) for v in a]))
+    third = np.sort(sims)[-3]
+    for w in (third, np.nextafter(third, f32(0)), np.nextafter(third, f32(2))):
+        for m in (1, 2, 3):
+            L.candidates([(0, 50)], q, weak=float(w), strong=0.5, max_num_weak=m)
+
+
+def _n_weak(L):
+    a = _thr_setup(L)
+    q = near(a[0], 3, 0.01)
+    nw = _ref_result(_thr_setup, [(0, 50)], q, weak=0.8, strong=0.9)[0][4]
+    for m in (nw - 1, nw, nw + 1):
+        L.candidates([(0, 50)], q, weak=0.8, strong=0.9, max_num_weak=m)
+
+
+def _bad_vectors(L):
+    L.configure(2, 4, 65)
+    a = vecs(12, 3, 65)
+    L.append([0, 0], [1, 2], a[:2])
+    zero = np.zeros(65, f32); inf = a[2].copy(); inf[64] = np.inf; nan = a[2].copy(); nan[3] = np.nan
+    huge = np.full(65, 3e19, f32)                     # finite elements, n2 overflows
+    tiny = np.full(65, 1e-30, f32)                    # n2 underflows to zero
+    for bad in (zero, inf, nan, huge, tiny):
+        L.append([0, 0], [5, 6], np.stack([a[2], bad]))       # refused as a whole: the good row before the bad one is not stored
+        L.read([0])
+        L.candidates([(0, 9), (1, 9)], np.stack([a[0], bad]), min_gap=0)      # the bad job's neighbour is answered
+        L.candidates([(0, 9)], bad, min_gap=0)
+    L.append([0, 0], [5, 6], a[1:3])
+    L.read([0])
+
+
+FIVE = (0, 3, 17, 1, 40)
+
+
+def _five_setup(d):
+    d.configure(5, 40, 63)
+    for s, n in enumerate(FIVE):
+        if n:
+            d.append([s] * n, list(range(s, s + 2 * n, 2)), vecs(200 + s, n, 63))
+
+
+def _five_streams(L):
+    _five_setup(L)
+    q = np.stack([near(vecs(200 + s, max(n, 1), 63)[n // 2], s, 0.05) for s, n in enumerate(FIVE)])
+    jobs = [(s, 200) for s in range(5)]
+    L.candidates(jobs, q, weak=0.3, strong=0.5)
+    L.candidates(jobs, q, weak=0.3, strong=0.5)             # two calls, the same bits
+    for s in range(5):                                      # a job alone
+        L.candidates([jobs[s]], q[s], weak=0.3, strong=0.5)
+    L.candidates([jobs[1], jobs[4]], q[[1, 4]], weak=0.3, strong=0.5)
+    L.candidates([], np.zeros((0, 63), f32))                # a valid no-op
+    L.read(range(5))
+
+
+def _interleaved_append(L):
+    """one append call over several streams, a stream more than once, and a second configure that empties the store"""
+    L.configure(3, 4, 64)
+    a = vecs(31, 6, 64)
+    L.append([2, 0, 2, 1, 0, 2], [4, 1, 6, 0, 3, 9], a)
+    L.read([0, 1, 2])
+    L.candidates([(0, 10), (2, 10)], a[[4, 2]], min_gap=0, weak=0.5, strong=0.6)
+    L.configure(2, 2, 64)
+    L.read([0, 1])
+    L.append([1], [0], a[:1])
+    L.read([0, 1])
+
+
+def _full_stream(L):
+    L.configure(2, 3, 64)
+    a = vecs(9, 5, 64)
+    L.append([0, 0, 0], [0, 1, 2], a[:3])
+    L.append([0], [3], a[3:4])                  # full
+    L.append([1, 0], [0, 3], a[3:5])            # full, and the row before it in the call is not stored either
+    L.append([1], [0], a[3:4])                  # the other stream still takes rows
+    L.append([1, 1, 1], [1, 2, 3], a[:3])       # the call's third row does not fit
+    L.append([1, 1], [1, 2], a[:2])
+    L.read([0, 1])
+    L.candidates([(0, 30), (1, 30)], a[[1, 3]])
+
+
+def _refusals(L):
+    L.unconfigured()
+    L.append([0], [0], vecs(1, 1, 64)); L.candidates([(0, 1)], vecs(1, 1, 64))
+    for ns, cap, dim in ((1, 4, 0), (1, 4, 4097), (0, 4, 64), (1, 0, 64), (-1, 4, 64), (1, 4, -3)):
+        L.configure(ns, cap, dim)
+    L.configure(1, 1, 4096); L.configure(1, 1, 1)
+    L.configure(3, 4, 64)
+    a = vecs(2, 4, 64)
+    L.append([0, 0], [5, 7], a[:2])
+    L.append([3], [9], a[:1]); L.append([-1], [9], a[:1])                       # unknown stream
+    L.append([0], [7], a[:1]); L.append([0], [6], a[:1]); L.append([0, 0], [9, 9], a[:2]); L.append([1], [-1], a[:1])   # ids
+    L.read([0, 1, 2])
+    q = a[2:3]
+    L.candidates([(0, 7)], q); L.candidates([(0, 8)], q, min_gap=0)             # kf_id above the last stored id
+    L.candidates([(1, -1)], q); L.candidates([(1, 0)], q)
+    L.candidates([(3, 9)], q); L.candidates([(-1, 9)], q)
+    two = a[2:4]
+    L.candidates([(0, 9), (0, 9)], two); L.candidates([(1, 9), (0, 9)], two); L.candidates([(0, 9), (1, 9)], two)
+    L.candidates([(0, 9)], q, min_gap=-1); L.candidates([(0, 9)], q, min_gap=0)
+    L.candidates([(0, 9)], q, max_num_weak=-1); L.candidates([(0, 9)], q, max_num_weak=0)
+    for t in (np.nan, np.inf, -np.inf):
+        L.candidates([(0, 9)], q, weak=t); L.candidates([(0, 9)], q, strong=t)
+    L.candidates([(0, 9)], q, weak=-3e38, strong=3e38)
+    L.read([0, 1, 2])
+
+
+CASES = {}
+for _d in (1, 63, 64, 65, 128, 255, 256, 257, 1280, 4096):
+    CASES["dim_%d" % _d] = _dim_case(_d)
+for _n in (0, 1, 3, 4, 5, 15, 16, 17, 63, 64, 65):
+    CASES["rows_%d" % _n] = _rows_case(_n)
+CASES["rows_600_dim_4096"] = _rows_case(600, 4096)
+CASES.update({
+    "gap_by_id": _gap,
+    "tie_one_wave": _tie_case((1, 2), 8),
+    "tie_two_waves": _tie_case((2, 6), 8),
+    "tie_lower_id_in_a_later_wave": _tie_case((5, 16), 20),
+    "tie_three_groups": _tie_case((9, 30, 47), 50),
+    "all_nonpositive": _nonpositive,
+    "strong_at_own_bits": _strong,
+    "weak_at_own_bits": _weak,
+    "n_weak_at_max": _n_weak,
+    "bad_vectors": _bad_vectors,
+    "five_streams": _five_streams,
+    "interleaved_append": _interleaved_append,
+    "full_stream": _full_stream,
+    "refusals": _refusals,
+})
+
+_REF = {}
+
+
+def reference(name):
+    """a case's log over the reference, computed once"""
+    if name not in _REF:
+        L = Log(RefDriver()); CASES[name](L); _REF[name] = L.seen
+    return _REF[name]
+
+
+def run(name, drv):
+    L = Log(drv); CASES[name](L)
+    return L.seen
+
+
+def compare(got, want):
+    if len(got) != len(want):
+        return False, "%d entries against %d" % (len(got), len(want))
+    for i, (g, w) in enumerate(zip(got, want)):
+        if g != w:
+            return False, "entry %d (%s): %r against the reference's %r" % (i, w[0], g[:4] if w[0] != "read" else g[:4], w[:4])
+    return True, "%d entries equal" % len(got)
+
+
+def check(name, drv):
+    ok, msg = compare(run(name, drv), reference(name))
+    assert ok, name + ": " + msg
+    return msg
