@@ -11,6 +11,13 @@ static std::string g_err;
 
 extern "C" const char *emu_pg_error() { return g_err.c_str(); }
 
+// the SE(3) functions of the kernel one by one (tests/test_pose_graph_se3_mpmath.py compares them with 60-digit values)
+extern "C" void emu_pg_log(const double *T7, double *xi6) { pg_log(T7, xi6); }
+extern "C" void emu_pg_exp(const double *xi6, double *T7) { pg_exp(xi6, T7); }
+extern "C" void emu_pg_jr_inv(const double *e6, double *J36) { pg_jr_inv(e6, J36); }
+extern "C" void emu_pg_edge_linearise(const double *M7, const double *Ta7, const double *Tb7, double *out78) { pg_edge_linearise(M7, Ta7, Tb7, out78); }
+extern "C" int emu_pg_ldlt6_inv(const double *D36, double *inv36) { return pg_ldlt6_inv(D36, inv36) ? 1 : 0; }
+
 // trace_or_null: [njobs][LM_TRACE_STRIDE] doubles as svslam_lm_trace keeps them
 extern "C" int emu_pose_graph(int njobs, EmuJob *jobs, int total_kf, double *poses, const uint8_t *fixed, int total_edges, const int *ea,
                               const int *eb, const double *meas, int total_pts, const int *anchor, double *pts, int iters, double *trace_or_null)

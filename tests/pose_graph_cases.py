@@ -5,7 +5,9 @@ A case is a keyframe chain with noisy odometry: the start is the dead-reckoned t
 the loop edges (ground-truth relative poses) carry the whole residual — the situation at LoopClosure::PoseGraphOptimization.
 Rotations are a few tenths of a radian per edge, mostly about one axis, so the heading passes a full turn on the longer chains.
 Sizes: N = 1, 2, 3; 17, 63, 64, 65, 257 (the kernel is one wave per graph: edge and vertex loops stride by 64); loop spans 9, 10,
-11 (the forward sweep deals a row's blocks over 10 lane groups)."""
+11 (the forward sweep deals a row's blocks over 10 lane groups).
+new_cases() adds the other graphs the ABI allows (edges listed from either end, permuted edges and vertices, any fixed vertex, a
+repeated edge, a vertex without edges, -q) and the branch limits of the SE(3) functions (residual rotations up to pi, overflow)."""
 import numpy as np
 
 import ref_pose_graph as rpg
@@ -22,6 +24,29 @@ TOL_SMALL = dict(t=1e-6, q=1e-7, pts=1e-6, lam=1e-4, chi2=2e-5)      # N <= 65: 
 # Ten times the measured differences is below the N <= 65 tolerances by many orders, so the case is far from the "too
 # ill-conditioned" limit and keeps the issue's odometry noise.
 TOL_257 = dict(t=5.5e-13, q=1.1e-14, pts=7.2e-13, lam=3.4e-13, chi2=1.6e-12)
+# The SE(3) functions one by one against 60-digit values of another formulation (tests/pose_graph_direct.py, which defines the error
+# of an entry relative to the scale of the terms it is summed from, and the five classes of the rotation angle: below 1e-10, up to
+# 0.01, up to 0.2, up to 3.1, pi - 1e-6).  MEASURED, the largest error of tests/ref_pose_graph.py per function and class:
+#   exp, rotation      0        1.1e-19  1.1e-16  2.2e-16  1.1e-16
+#   exp, translation   4.5e-11  5.5e-11  5.7e-16  1.5e-16  2.3e-16    Sophus: V = R below 1e-10 rad (|u| theta / 2), and (1 - cos) / theta^2
+#                                                                     cancels as eps / theta above it
+#   log                1.4e-16  8.6e-11  2.0e-16  1.9e-16  1.8e-16    Sophus' c cancels as eps / theta^2 just above 1e-10 rad (seen where the
+#                                                                     translation lies along a coordinate axis; 5e-21 absolute)
+#   Jr^-1              5.6e-17  5.6e-17  8.1e-15  3.8e-16  5.6e-11    the closed form cancels at the 0.1 rad switch and as eps / (pi - theta)
+#   linearise: e       4.5e-16  6.5e-16  2.1e-16  3.9e-16  1.8e-16
+#              J_a     2.0e-16  5.5e-16  5.5e-15  7.8e-16  4.6e-11
+#              -J_b    2.3e-16  3.6e-16  5.0e-15  5.6e-16  4.1e-11
+#   6x6 LDL^T inverse  3.0e-16 (relative to the largest entry of the inverse; condition numbers up to 1e5)
+# BOUND: ten times the measurement, not below 4 ulp (4 x 2^-52 = 8.9e-16); the emulation of the kernel is held to the same numbers.
+# test_pose_graph_se3_mpmath.py prints the measurement again and asserts the bound for both.
+# The figures depend on the libm: they were measured with glibc's sin / cos / atan, and where an entry sits on a cancellation (exp's
+# translation and log in the second class, Jr^-1 and the Jacobians in the last) one ulp of a library call is the whole error.  Ten
+# times leaves room for another correctly working libm; if one of these classes fails on a new platform, measure again before
+# anything else.
+TOL_DIRECT = dict(exp_R=(8.9e-16, 8.9e-16, 1.1e-15, 2.2e-15, 1.1e-15), exp_t=(4.5e-10, 5.5e-10, 5.7e-15, 1.5e-15, 2.3e-15),
+                  log=(1.4e-15, 8.6e-10, 2.0e-15, 1.9e-15, 1.8e-15), jr_inv=(8.9e-16, 8.9e-16, 8.0e-14, 3.8e-15, 5.6e-10),
+                  lin_e=(4.5e-15, 6.5e-15, 2.1e-15, 3.9e-15, 1.8e-15), lin_Ja=(2.0e-15, 5.5e-15, 5.5e-14, 7.8e-15, 4.6e-10),
+                  lin_Jr=(2.3e-15, 3.6e-15, 5.0e-14, 5.6e-15, 4.1e-10), ldlt=(3.0e-15,))
 
 
 def _truth(n, rng, rot_step, origin=(0.0, 0.0, 0.0)):
@@ -91,7 +116,161 @@ def _odometry_only(n, seed):
     return job
 
 
+def _reversed(job, which):
+    """edge k with which[k] listed from its other end: (a, b, M) -> (b, a, M^-1).  The residual becomes -Ad(M) e, another vector of
+    another norm, so the graph is a different least-squares problem wherever a residual is not 0; it has the same zero-residual
+    states."""
+    ea, eb, meas = job["edges"]
+    ea, eb, meas = ea.copy(), eb.copy(), meas.copy()
+    for k in range(len(ea)):
+        if which[k]:
+            ea[k], eb[k] = eb[k], ea[k]
+            meas[k] = rpg.se3_inv(meas[k])
+    return dict(job, edges=(ea, eb, meas))
+
+
+def _edge_perm(job, seed):
+    ea, eb, meas = job["edges"]
+    p = np.random.default_rng(seed).permutation(len(ea))
+    return dict(job, edges=(ea[p].copy(), eb[p].copy(), meas[p].copy()))
+
+
+def _vertex_perm(job, seed):
+    """vertex v becomes number p[v]: poses, fixed flags, edge ends and anchors follow"""
+    n = len(job["poses"])
+    p = np.random.default_rng(seed).permutation(n).astype(np.int32)
+    poses = np.zeros((n, 7)); fixed = np.zeros(n, np.uint8)
+    poses[p] = job["poses"]; fixed[p] = job["fixed"]
+    ea, eb, meas = job["edges"]
+    out = dict(job, poses=poses, fixed=fixed, edges=(p[ea], p[eb], meas.copy()))
+    if job.get("anchor") is not None:
+        an = job["anchor"].copy(); an[an >= 0] = p[an[an >= 0]]
+        out["anchor"] = an
+    return out
+
+
+def _isolated_free(job, at, pose):
+    """a free vertex without an edge inserted as number `at`, one point anchored on it.  Its quaternion must have |q|^2 == 1.0 in
+    floating point: exp(0) T then leaves every bit of it (se3_mul renormalises only where the squared norm is not 1)."""
+    n = len(job["poses"])
+    up = lambda v: np.where(v >= at, v + 1, v).astype(np.int32)
+    ea, eb, meas = job["edges"]
+    an = up(job["anchor"]); an[job["anchor"] < 0] = -1
+    return dict(poses=np.insert(job["poses"], at, pose, axis=0), fixed=np.insert(job["fixed"], at, 0), edges=(up(ea), up(eb), meas.copy()),
+                anchor=np.concatenate([an, [at]]).astype(np.int32), pts=np.concatenate([job["pts"], [[1.5, -2.0, 9.0]]]))
+
+
+def _neg_w(job, which):
+    poses = np.array(job["poses"]); poses[which, :4] *= -1.0
+    return dict(job, poses=poses)
+
+
+def _theta(theta, seed):
+    """three vertices, 0 fixed, edges (1, 0), (2, 1), (2, 0); the start satisfies the two chain edges, and the loop measurement is
+    exp(xi) T_2 T_0^-1 with |xi[3:]| = theta and xi[:3] = 0.4 N(0, 1): the loop edge starts with a residual rotation of theta"""
+    rng = np.random.default_rng(seed)
+    job = make(3, seed, noise_t=0.05, noise_r=0.01)
+    P = job["poses"]; ea, eb, meas = job["edges"]
+    ax = rng.standard_normal(3); ax /= np.linalg.norm(ax)
+    xi = np.concatenate([0.4 * rng.standard_normal(3), theta * ax])
+    xi[3:] *= theta / np.linalg.norm(xi[3:])
+    Ml = rpg.se3_mul(rpg.se3_exp(xi), rpg.se3_mul(P[2], rpg.se3_inv(P[0])))
+    return dict(job, edges=(np.append(ea, 2).astype(np.int32), np.append(eb, 0).astype(np.int32), np.vstack([meas, Ml])))
+
+
+THETAS = {"theta_1e-11": 1e-11, "theta_0.0999": 0.0999, "theta_0.1001": 0.1001, "theta_0.5": 0.5, "theta_2.0": 2.0, "theta_3.0": 3.0,
+          "theta_pi-1e-5": np.pi - 1e-5}
+
+
+def _pi(sign):
+    """_optimum's chain (identity rotations, dyadic translations) with a loop edge (4, 1) whose measurement has the quaternion
+    (0.6, 0, 0.8, sign 1e-11): T_4 T_1^-1 has the quaternion (0, 0, 0, 1) exactly, so the residual's quaternion is the conjugate of
+    the measurement's and its w = sign 1e-11 lies inside |w| < 1e-10, the branch of pg_log that returns +-pi / |v| — one case per
+    sign.  The residual rotation is pi to 2e-11.
+    EXACTLY at pi the coefficient (1 + cos theta) / (2 theta sin theta) of pg_jr_inv is 0 / 0 in floating point: the host's libm
+    gives cos(fl(pi)) = -1 and the quotient 0; one ulp in the device's cos moves it by O(0.1).  The Jacobians, and with them every
+    trial, are therefore not comparable between two correct libms: ON THE DEVICE these two cases compare chi2_before only.  That
+    checks little: that the branch region gives a finite residual of the right norm.  It does NOT see the sign of the branch —
+    omega -> -omega turns V^-1 into its transpose, and |V^-1 t| = |V^-T t| (the cross term t^T (I + c W^2) W t is 0), so chi2_before
+    is the same for both signs — and it cannot tell the branch from the atan form either, which gives the same angle to 2e-11.  The
+    sign shows from the first trial on, through the Jacobian: the host emulation, which shares the reference's libm, compares
+    everything, and it alone kills the "+pi on both sides" mutant."""
+    job = _optimum()
+    ea, eb, meas = job["edges"]
+    Ml = np.array([0.6, 0.0, 0.8, sign * 1e-11, 0.75, -1.25, 0.5])
+    return dict(job, edges=(np.append(ea, 4).astype(np.int32), np.append(eb, 1).astype(np.int32), np.vstack([meas, Ml])))
+
+
+CHI2_BEFORE_ONLY_ON_DEVICE = ("pi_plus", "pi_minus")
+_BASE = dict(n=12, seed=13, loops=[(11, 1), (8, 3)])          # the graph `reversed`, `reversed_all` and the permutations are made from
+
+
+def base_graph(**kw):
+    return make(_BASE["n"], _BASE["seed"], loops=_BASE["loops"], **kw)
+
+
+def new_cases():
+    """graph kinds the ABI allows beside the chain with edges (k, k - 1), (i > j): edges listed from either end, any edge order, any
+    vertex numbering, any fixed vertex, a repeated edge, a vertex without edges, either quaternion sign; and the branch limits of
+    pg_log / pg_exp / pg_jr_inv (theta_*, pi_*)"""
+    c = {}
+    b = base_graph(pts="one")
+    ne = len(b["edges"][0])
+    c["reversed"] = _reversed(b, np.arange(ne) % 2 == 1)
+    c["reversed_all"] = _reversed(b, np.ones(ne, bool))
+    f = make(10, 31, loops=[(9, 1), (6, 2)], pts="one"); f["fixed"][0] = 0; f["fixed"][9] = 1
+    c["fixed_last"] = f
+    c["fixed_two_ends"] = make(11, 32, loops=[(10, 1), (7, 3)], fixed_extra=[10], pts="several")
+    c["edge_perm"] = _edge_perm(b, 33)
+    c["vertex_perm"] = _vertex_perm(b, 34)
+    d = base_graph(pts="one"); ea, eb, meas = d["edges"]
+    k = int(np.flatnonzero((ea == 8) & (eb == 3))[0])
+    d["edges"] = (np.append(ea, ea[k]).astype(np.int32), np.append(eb, eb[k]).astype(np.int32), np.vstack([meas, meas[k]]))
+    c["duplicate_edge"] = d
+    c["isolated_free"] = _isolated_free(make(9, 35, loops=[(8, 1)], pts="one"), 4, np.array([0.5, -0.5, 0.5, 0.5, 3.0, -1.0, 2.0]))
+    c["neg_w"] = _neg_w(make(14, 15, loops=[(12, 2), (9, 5)], pts="one"), [0, 3, 4, 9, 13])      # `nested` with five poses as -q
+    for name, th in THETAS.items():
+        c[name] = _theta(th, 36)
+    c["pi_plus"] = _pi(1.0)
+    c["pi_minus"] = _pi(-1.0)
+    c["overflow"] = _overflow()
+    return c
+
+
+def _overflow(s=1e154):
+    """_optimum's chain scaled to translations of 1e154 m with a contradicting loop edge (3, 1): chi2 (3e307) is finite, the
+    rotation-rotation diagonal of H (|t|^2 ~ 1e309) is not.  lambda0 = 1e-5 max diag H is then infinite, every pivot of the
+    factorisation is (`s < INFINITY` fails: the failed-factorisation path), the trial's chi2 is replaced by DBL_MAX, rho is -inf, and
+    lambda x nu stays infinite: the non-finite-lambda stop after ONE rejected trial, the poses with their input bits.
+    Ten rejected trials through a failed factorisation cannot be reached with finite inputs: between the largest scale at which H
+    stays finite (3e153: the solve succeeds and LM runs as usual) and the smallest at which its diagonal overflows (4e153) nothing
+    else overflows first, and an infinite diagonal makes lambda infinite at once."""
+    job = _optimum(4)
+    job["poses"][:, 4:] *= s
+    ea, eb, meas = job["edges"]
+    meas = meas.copy(); meas[:, 4:] *= s
+    q = np.array([0.1, 0.2, -0.1, 0.0]); q[3] = np.sqrt(1.0 - q[:3] @ q[:3])
+    Ml = np.concatenate([q, s * np.array([1.25, -0.5, 3.5])])
+    return dict(poses=job["poses"], fixed=job["fixed"],
+                edges=(np.append(ea, 3).astype(np.int32), np.append(eb, 1).astype(np.int32), np.vstack([meas, Ml])))
+
+
+def consistent_pair(seed=37):
+    """the base graph with measurements that one state satisfies exactly (chain and loop measurements composed from one truth), the
+    start pushed off it; returns (as listed, every edge reversed).  Reversing an edge turns its residual e into -Ad(M) e: the two
+    graphs weigh a non-zero residual differently and share an optimum only where it is a zero-residual state, as here.  (With the
+    noisy odometry of `reversed_all` the two optima lie 0.045 m apart.)"""
+    job = base_graph(noise_t=0.0, noise_r=0.0, start_noise=0.01)
+    return job, _reversed(job, np.ones(len(job["edges"][0]), bool))
+
+
 def cases():
+    c = _old_cases()
+    c.update(new_cases())
+    return c
+
+
+def _old_cases():
     c = {}
     c["empty"] = dict(poses=np.zeros((0, 7)), fixed=np.zeros(0, np.uint8), edges=None)
     c["n1"] = dict(poses=np.array([[0, 0, 0, 1, 1.0, 2.0, 3.0]]), fixed=np.ones(1, np.uint8), edges=None,
@@ -131,6 +310,12 @@ def cases():
 # to noise (its loop measurements contradict the odometry) and runs 12.
 ITERS = dict(empty=22, n1=22, edgeless=22, optimum=22, zero_chain=22, ten_failed=22, n2=2, n3_loop_to_fixed=3, loop_full=5, loop_fixed_end=3, nested=7, crossing=5,
              span2=3, fixed_mid=3, both_fixed_edge=2, spans_9_10_11=8, rejected=12, n17=6, n63=11, n64=12, n65=9, n257=15)
+# the new cases by the same rule (theta_3.0, theta_pi-1e-5 and pi_* keep descending with |rho| > 1e-9 through all 22: the residual
+# rotation near pi makes LM slow; `overflow` stops itself after one trial).  No seed had to be replaced: the first seed tried for
+# each case keeps the margin (smallest |rho| of a compared trial: 1.3e-9, fixed_last).
+ITERS.update({"reversed": 5, "reversed_all": 4, "fixed_last": 3, "fixed_two_ends": 2, "edge_perm": 5, "vertex_perm": 5, "duplicate_edge": 5,
+              "isolated_free": 4, "neg_w": 7, "theta_1e-11": 4, "theta_0.0999": 4, "theta_0.1001": 4, "theta_0.5": 4, "theta_2.0": 13,
+              "theta_3.0": 22, "theta_pi-1e-5": 22, "pi_plus": 22, "pi_minus": 22, "overflow": 22})
 
 _REF = {}
 TRACE_STRIDE = 8 + 6 * 408        # svslam_lm_trace's per-job record block
@@ -189,7 +374,8 @@ def reference(name, jac_mode="analytic", solver="dense", h_order="edge"):
     """computed once per process and shared; callers must not modify it"""
     key = (name, jac_mode, solver, h_order)
     if key not in _REF:
-        _REF[key] = rpg.pose_graph(cases()[name], ITERS[name], jac_mode, solver, h_order)
+        with np.errstate(over="ignore", invalid="ignore"):          # `overflow` is meant to
+            _REF[key] = rpg.pose_graph(cases()[name], ITERS[name], jac_mode, solver, h_order)
     return _REF[key]
 
 
@@ -230,7 +416,9 @@ def diffs(got, ref):
     gt, rt = np.asarray(got["trace"]).reshape(-1, 6), ref["trace"]
     m = min(len(gt), len(rt))
     for a, b in zip(gt[:m], rt[:m]):
-        if b[1] > 0:
+        if b[1] == np.inf:                      # `overflow`: an infinite lambda has to be that
+            d["lam"] = max(d["lam"], 0.0 if a[1] == np.inf else np.inf)
+        elif b[1] > 0:
             d["lam"] = max(d["lam"], abs(a[1] - b[1]) / b[1])
         for k in (2, 3):
             if np.isfinite(b[k]) and b[k] < 1e300:
@@ -267,3 +455,39 @@ def compare(got, ref, tol, allow_tie=False):
         d["chi2"] = max(d["chi2"], abs(a - b) / max(abs(b), 1e-12))
     bad = {k: v for k, v in d.items() if v > tol[k]}
     return (not bad), ties, "differences %s exceed %s" % (bad, tol) if bad else "ok %s" % d
+
+
+POINT_ROUNDING = 3e-14      # a point re-anchored on a pose that did not move: two rigid maps of ~8 rounded operations each on
+                            # magnitudes below |x| + |t| < 16 m: 16 x 2^-53 x 16 = 2.8e-14
+
+
+def check_new_case(name, job, got, run, same_libm):
+    """what the new cases assert beside compare(), on the host emulation and on the device alike.  run(jobs, iters) -> results with
+    their traces; same_libm: the implementation shares the reference's libm and arithmetic (the host emulation)"""
+    if name == "isolated_free":
+        assert np.array_equal(got["poses"][4], np.asarray(job["poses"])[4])                    # the input bits
+        assert np.abs(got["pts"][-1] - job["pts"][-1]).max() <= POINT_ROUNDING
+    if name == "neg_w":
+        (pos,) = run([cases()["nested"]], ITERS["nested"])
+        ok, ties, msg = compare(got, pos, TOL_SMALL)
+        assert ok and ties == 0, "neg_w against the same job with +q: " + msg
+        d = diffs(got, pos)
+        print("neg_w against nested:", d)
+        if same_libm:       # -q goes through the same roundings as q
+            assert d["t"] == 0 and d["q"] == 0 and d["pts"] == 0 and np.array_equal(got["trace"], pos["trace"])
+    if name == "overflow":
+        tr = got["trace"]
+        assert got["iters"] == 1 and got["trials"] == 1 and len(tr) == 1
+        assert tr[0, 1] == np.inf and tr[0, 3] == rpg.DBL_MAX and tr[0, 4] == -np.inf and tr[0, 5] == 0.0
+        assert np.array_equal(got["poses"], np.asarray(job["poses"]))                          # the input bits
+
+
+def emu_build(src_root, out_dir, opt="-O2"):
+    """tests/cpp/pg_host_emu of the tree at src_root as a shared library in out_dir (no contraction: the device code has none)"""
+    import ctypes as C
+    import os
+    import subprocess
+    so = os.path.join(str(out_dir), "libpg_host_emu.so")
+    subprocess.check_call(["g++", opt, "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
+                           os.path.join(str(src_root), "tests", "cpp", "pg_host_emu", "emu.cpp"), "-o", so])
+    return C.CDLL(so)

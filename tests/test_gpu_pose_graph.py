@@ -31,6 +31,12 @@ def test_against_the_reference(ctx, ties, name):
     ref = pc.reference(name)
     (got,) = ctx.pose_graph([job], iters=pc.ITERS[name])
     got["trace"] = ctx.lm_trace(job=0)
+    if name in pc.CHI2_BEFORE_ONLY_ON_DEVICE:       # theta = pi: the Jacobian is 0 / 0 (pose_graph_cases._pi).  A finite residual of the
+        # right norm is all this sees: not the sign of the branch, which the host emulation checks
+        d = abs(got["chi2_before"] - ref["chi2_before"]) / ref["chi2_before"]
+        print(name, "chi2_before differs by", d)
+        assert d <= pc.TOL_SMALL["chi2"], (name, got["chi2_before"], ref["chi2_before"])
+        return
     ok, tied, msg = pc.compare(got, ref, pc.tol_of(name), allow_tie=True)
     print(name, msg)
     if tied:
@@ -45,6 +51,13 @@ def test_against_the_reference(ctx, ties, name):
     if name in ("empty", "n1", "edgeless"):
         assert got["iters"] == 0 and got["trials"] == 0 and got["chi2_before"] == 0.0 and got["chi2_after"] == 0.0
 
+    def run(jobs, iters):
+        out = ctx.pose_graph(jobs, iters=iters)
+        for i, o in enumerate(out):
+            o["trace"] = ctx.lm_trace(job=i)
+        return out
+    pc.check_new_case(name, job, got, run, same_libm=False)
+
 
 @pytest.mark.parametrize("name", pc.FULL_RUN_CASES)
 def test_final_state_at_the_reference_s_22_iterations(ctx, name):
@@ -56,9 +69,14 @@ def test_final_state_at_the_reference_s_22_iterations(ctx, name):
 
 
 def test_batch_independence_and_determinism(ctx):
-    """every case in one call (empty and edgeless jobs included), the same call again, and every job alone: the same bits"""
+    """every case in one call (empty and edgeless jobs included), the same call again, and every job alone: the same bits.
+    (Calls of at most 32 jobs, the context's max_jobs, so that every job of a call has a trace; test_jobs_beyond_max_jobs is about more.)"""
     c = pc.cases()
-    names = list(c)
+    for lo in range(0, len(c), 32):
+        _together_again_alone(ctx, c, list(c)[lo:lo + 32])
+
+
+def _together_again_alone(ctx, c, names):
     together = ctx.pose_graph([c[n] for n in names], iters=22)
     traces = [ctx.lm_trace(job=i) for i in range(len(names))]
     again = ctx.pose_graph([c[n] for n in names], iters=22)
@@ -70,6 +88,54 @@ def test_batch_independence_and_determinism(ctx):
             assert np.array_equal(alone[k], together[i][k]) and np.array_equal(again[i][k], together[i][k]), (n, k)
         for k in ("iters", "trials", "chi2_before", "chi2_after"):
             assert alone[k] == together[i][k] == again[i][k], (n, k)
+
+
+def _same_bits(a, b, what):
+    for k in ("poses", "pts"):
+        assert np.array_equal(a[k], b[k]), (what, k)
+    for k in ("iters", "trials", "chi2_before", "chi2_after"):
+        assert a[k] == b[k], (what, k)
+
+
+def test_jobs_beyond_max_jobs(ctx):
+    """40 jobs on a context with max_jobs = 32 and the trace on: jobs 32 .. 39 have no trace slot (the kernel's trace pointer is
+    null for them) and return the bits they return alone, reading their trace is refused, jobs 0 .. 31 are traced as ever"""
+    c = pc.cases()
+    small = ["n2", "n3_loop_to_fixed", "span2", "reversed", "fixed_last", "theta_0.5", "duplicate_edge", "isolated_free"]
+    names = [small[i % 8] for i in range(32)] + small[3:] + small[:3]
+    got = ctx.pose_graph([c[n] for n in names], iters=4)
+    traces = [ctx.lm_trace(job=i) for i in range(32)]
+    for j in (32, 39, 40):
+        with pytest.raises(RuntimeError, match="out of range"):
+            ctx.lm_trace(job=j)
+    for i in range(32):
+        assert len(traces[i]) == got[i]["trials"] > 0 and traces[i][0, 2] == got[i]["chi2_before"], (i, names[i])
+        assert np.array_equal(traces[i], traces[i % 8]), (i, names[i])
+    for i in range(32, 40):
+        (alone,) = ctx.pose_graph([c[names[i]]], iters=4)
+        _same_bits(got[i], alone, (i, names[i]))
+        assert alone["trials"] > 0
+
+
+def test_the_kept_scratch_carries_nothing_over(svs):
+    """on a fresh context: a small graph, n65 (which makes the context replace its buffer by a larger one, kept from then on), the
+    small graph again, now in memory that n65 left its solver state in: the first and third results are the same bits, trace included"""
+    c = pc.cases()
+    ctx = svs.Context(64, 32, max_slots=1, max_jobs=2)
+    ctx.lm_trace(True)
+    try:
+        _small_big_small(ctx, c)
+    finally:
+        ctx.close()
+
+
+def _small_big_small(ctx, c):
+    (first,) = ctx.pose_graph([c["reversed"]], iters=22); t1 = ctx.lm_trace(job=0)
+    (big,) = ctx.pose_graph([c["n65"]], iters=pc.ITERS["n65"])
+    (third,) = ctx.pose_graph([c["reversed"]], iters=22); t3 = ctx.lm_trace(job=0)
+    assert big["trials"] > 0 and first["trials"] > 0
+    _same_bits(first, third, "reversed")
+    assert np.array_equal(t1, t3)
 
 
 def test_refusals_write_nothing(ctx):

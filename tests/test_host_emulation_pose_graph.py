@@ -2,9 +2,7 @@
 every case of pose_graph_cases.py: the plan (free indices, envelope, incidence lists), the closed-form linearisation, the
 block-skyline LDL^T, the two sweeps and g2o's LM decisions are checked here without a device.  Not a replacement for
 tests/test_gpu_pose_graph.py: the compiler, the ISA, the barriers and the launch are not in it."""
-import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,15 +10,11 @@ import pytest
 import pose_graph_cases as pc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU = os.path.join(ROOT, "tests", "cpp", "pg_host_emu")
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    d = tmp_path_factory.mktemp("pg_host_emu")
-    so = str(d / "libpg_host_emu.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(EMU, "emu.cpp"), "-o", so])
-    return C.CDLL(so)
+    return pc.emu_build(ROOT, tmp_path_factory.mktemp("pg_host_emu"))
 
 
 @pytest.mark.parametrize("name", list(pc.cases()))
@@ -39,6 +33,7 @@ def test_kernel_source_on_the_host_against_the_reference(emu, name):
         assert got["iters"] == 1 and got["trials"] == 1 and got["trace"][0, 4] == 0.0          # stopped by the rho == 0 rule
     if name in ("empty", "n1", "edgeless"):
         assert got["iters"] == 0 and got["trials"] == 0 and got["chi2_before"] == 0.0 and got["chi2_after"] == 0.0
+    pc.check_new_case(name, job, got, lambda jobs, iters: pc.emu_run(emu, jobs, iters), same_libm=True)
 
 
 @pytest.mark.parametrize("name", pc.FULL_RUN_CASES)
