@@ -436,7 +436,7 @@ int svslam_brief_default_pattern(int8_t out[1024]);
 /* ---- loop candidate search: a resident store of global image descriptors and the two-threshold rule ----------
  * Replaces stage 1 of the reference's loop closure, LoopClosure::LoopKeyframeCandidate (src/loopclosure.cpp:227-284) with
  * SimilarityScore (:173-180) and the normalisation of :128.  The global descriptor itself (the reference's MobileNetV2 vector of 1280
- * floats) is an INPUT; any vector of dim floats, 1 <= dim <= 4096, serves.  The store lives in the context, on the device:
+ * floats) is an input, or svslam_gdesc_* below; any vector of dim floats, 1 <= dim <= 4096, serves.  The store lives in the context, on the device:
  * nstreams x capacity normalised rows with their keyframe ids, ascending per stream.  Its layout is opaque.
  * The contract, met bit for bit by the kernel, its host build and tests/ref_loop_candidates.py; no tolerance anywhere:
  *   similarity  of two f32 vectors: 64 accumulators start at +0; accumulator l takes the elements e = l, l + 64, l + 128, ... below
@@ -484,6 +484,47 @@ int svslam_loop_candidates_batch(svslam_ctx *ctx, int njobs, svslam_lc_job *jobs
                                  const float *vecs /* [njobs][dim] */);
 int svslam_loopdb_count(svslam_ctx *ctx, int stream, int *count);
 int svslam_loopdb_read(svslam_ctx *ctx, int stream, int max_rows, int *kf_ids, float *vecs /* [max_rows][dim] */);
+
+/* ---- global image descriptor: a small convolutional network on a keyframe image ----------
+ * Replaces LoopClosure::ExtractFeatureVec (src/loopclosure.cpp:92-129): GaussianBlur(7 x 7), resize, blobFromImage and MobileNetV2 up to
+ * the global average pool.  The network is a table of layers; its WEIGHTS are an input (the reference's ONNX file is not part of this
+ * project; gdesc.py folds a torchvision state dict into params), the forward pass is this library's.  One job is level 0 of one
+ * pyramid slot, exactly what svslam_brief_describe_batch reads.  The contract (csrc/k_global_desc.h), met bit for bit by
+ * the kernels and their host build; every f32 output element is one chain in a fixed order, no split-K, no reassociation:
+ *   prep     blur: separable integer taps (8, 28, 56, 72, 56, 28, 8) / 256 (OpenCV's table for ksize 7, sigma 0), the horizontal sum
+ *            kept in full, the vertical sum over it, out = (v + 32768) >> 16, BORDER_REFLECT_101.
+ *            resize to out_w x out_h: per axis scale = (double)src / dst, f = (float)((d + 0.5) scale - 0.5), s = floor(f), f -= s;
+ *            s < 0: s = 0, f = 0; s >= src - 1: s = src - 1, f = 0; the second tap is min(s + 1, src - 1);
+ *            c1 = rint(f 2048), c0 = rint((1 - f) 2048) (half to even); S = p[s] c0 + p[s + 1] c1 along x;
+ *            out = (((b0 (S0 >> 4)) >> 16) + ((b1 (S1 >> 4)) >> 16) + 2) >> 2 along y.  Parity with OpenCV is not pinned.
+ *            blob: x[c] = ((float)pix - mean[c]) * scale, c = 0, 1, 2, planar.  The defaults (prep == NULL) are the reference's call:
+ *            224 x 224, mean (0.485, 0.456, 0.406), scale 1 / 255.
+ *   CONV3    dense 3 x 3, pad 1, stride 1 or 2; weights [cout][cin][3][3]; acc = bias[co], acc = fmaf(w, x, acc) over (ci, ky, kx)
+ *            row-major; a tap in the padding takes x = +0.0f and is part of the chain
+ *   DW3      depthwise 3 x 3, pad 1, stride 1 or 2, cin == cout; weights [c][3][3]; acc = bias[c], the 9 taps in (ky, kx) order
+ *   PW       1 x 1; weights [cout][cin]; acc = bias[co], acc = fmaf(w[co][ci], x[ci], acc), ci ascending
+ *   AVGPOOL  global, the last layer: s = +0, s = s + x over the pixels in row-major order, s / (float)(H W)
+ *   epilogue add_from >= 0 (PW with relu6 == 0 only; an earlier layer of the same C x H x W): one f32 add of that layer's output;
+ *            then, if relu6, v = v > 0 ? v : +0 and v = v < 6 ? v : 6.  A 3 x 3 layer's output size is (n + 2 - 3) / stride + 1.
+ * params holds, per layer in table order, the weights in the orders above followed by bias[cout]; AVGPOOL has none.
+ * svslam_gdesc_configure   Refused, nothing changed and the old network kept: a table that does not chain (cin != the previous cout,
+ *                          the first cin != 3), DW3 with cin != cout, a stride outside {1, 2}, a bad add_from, AVGPOOL missing or
+ *                          not last, a final dim outside 1 .. 4096, nparams not the table's total, a weight / mean / scale that is
+ *                          not finite, out_w or out_h < 1, no device memory.  workspace_bytes caps the activations of a chunk of
+ *                          jobs (0: 256 MiB); a cap below one job's share still runs one job at a time.
+ * svslam_gdesc_dim         cout of the last layer, 0 while no network is configured.
+ * svslam_gdesc_describe_batch  vecs [njobs][dim], raw (the loop store normalises at its append and in its search).  Refused, vecs
+ *                          untouched: no network, a slot out of range, an image below 4 x 4.  njobs == 0 is a valid no-op.  A job's
+ *                          result does not depend on the chunk size or on the other jobs; two calls give the same bits.
+ * svslam_gdesc_mobilenet_v2    the default table, 52 convolutions + the pool = 53 entries; returns the count, writes min(count, cap). */
+enum { SVSLAM_GD_CONV3 = 0, SVSLAM_GD_DW3 = 1, SVSLAM_GD_PW = 2, SVSLAM_GD_AVGPOOL = 3 };
+typedef struct svslam_gd_layer { int op, cin, cout, stride, relu6, add_from; } svslam_gd_layer;
+typedef struct svslam_gd_prep { int out_w, out_h; float mean[3]; float scale; long long workspace_bytes; } svslam_gd_prep;
+int svslam_gdesc_configure(svslam_ctx *ctx, int nlayers, const svslam_gd_layer *layers, const float *params, long long nparams,
+                           const svslam_gd_prep *prep);
+int svslam_gdesc_dim(svslam_ctx *ctx);
+int svslam_gdesc_describe_batch(svslam_ctx *ctx, int njobs, const int *slots, float *vecs /* [njobs][dim] */);
+int svslam_gdesc_mobilenet_v2(svslam_gd_layer *out, int cap);
 
 /* ---- shared-map bundle adjustment (BASELINE config 5; not in the reference) -----------
  * ONE local-BA problem whose landmarks are sharded over the GPUs of a node: every rank holds all
@@ -689,7 +730,8 @@ int svslam_sync(svslam_ctx *ctx);
  * 4 pose_only, 5 local_ba, 6 stereo_bm (units = jobs), 12 cloud_filter (units = points; appended
  * after the last number in use, nothing moved), 13 pose_graph (units = jobs; appended after 12, nothing moved),
  * 14 loop_verify (units = jobs; appended after 13, nothing moved), 15 brief (units = points; appended after 14, nothing moved),
- * 16 loop_candidates (units = rows compared, summed over the jobs; appended after 15, nothing moved).
+ * 16 loop_candidates (units = rows compared, summed over the jobs; appended after 15, nothing moved),
+ * 17 global_desc (units = jobs; appended after 16, nothing moved).
  * Development families follow and are NOT stable numbers: with stereo_bm taking 6, the
  * per-kernel split moved from 6-9 to 7-10 and the local-BA solver interval from 10 to 11.
  * A caller that passed those raw numbers must move with them (Python addresses them by name). */

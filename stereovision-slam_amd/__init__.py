@@ -22,6 +22,7 @@ ABI_SYMBOLS = [
     "svslam_pyramid_read_padded", "svslam_stereo_bm_batch", "svslam_stereo_bm_strip_rows", "svslam_dense_cloud_batch", "svslam_cloud_sor_batch", "svslam_cloud_voxel_grid", "svslam_debug_cloud_sor_climbs", "svslam_lk_batch", "svslam_gftt_batch", "svslam_gftt_eigmap", "svslam_triangulate_batch",
     "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect", "svslam_pose_graph_batch", "svslam_loop_verify_batch", "svslam_brief_describe_batch", "svslam_brief_default_pattern",
     "svslam_loopdb_configure", "svslam_loopdb_append_batch", "svslam_loop_candidates_batch", "svslam_loopdb_count", "svslam_loopdb_read",
+    "svslam_gdesc_configure", "svslam_gdesc_dim", "svslam_gdesc_describe_batch", "svslam_gdesc_mobilenet_v2",
     "svslam_track_batch", "svslam_rtrack_batch", "svslam_rtrack_upload",
     "svslam_sba_io_doubles", "svslam_sba_open", "svslam_sba_phase", "svslam_sba_close",
     "svslam_device_count", "svslam_dmap_keyframe_batch", "svslam_dmap_ba_collect", "svslam_dmap_read", "svslam_dmap_evicted", "svslam_sba_comm_unique_id", "svslam_sba_comm_init", "svslam_sba_comm_destroy", "svslam_sba_solve",
@@ -39,14 +40,16 @@ KERNEL_FAMILIES = {"ba_solve": 11}
 CLOUD_FAMILIES = {"cloud_filter": 12}      # the outlier removal and the voxel grid of the dense program (units = points); appended, nothing renumbered
 # svslam_pose_graph_batch, svslam_loop_verify_batch (units = jobs), svslam_brief_describe_batch (units = points); appended after 12,
 # 13 and 14, nothing renumbered; svslam_loop_candidates_batch (units = rows compared) appended after 15
-LOOP_FAMILIES = {"pose_graph": 13, "loop_verify": 14, "brief": 15, "loop_candidates": 16}
+# svslam_gdesc_describe_batch (units = jobs) appended after 16
+LOOP_FAMILIES = {"pose_graph": 13, "loop_verify": 14, "brief": 15, "loop_candidates": 16, "global_desc": 17}
 # the HIP kernel(s) behind each timing family at the batch operating point (what a rocprofv3 --kernel-trace --stats row is named)
 FAMILY_KERNELS = {"pyramid": ["k_pyr_fused"], "lk": ["k_lk"], "gftt": ["k_gftt_eig3", "k_gftt_select2"], "triangulate": ["k_triangulate"],
                   "pose_only": ["k_pose_only"], "local_ba": ["k_dmap_ba_gather", "k_ba_build", "k_local_ba_t", "k_dmap_ba_scatter"],
                   "ba_solve": ["k_local_ba_t"], "stereo_bm": ["k_bm_fill", "k_stereo_bm", "k_dense_cloud"],
                   "cloud_filter": ["k_cf_keys", "k_cf_gather", "k_cf_knn", "k_vg_keys", "k_vg_heads", "k_vg_starts", "k_vg_reduce"],
                   "pose_graph": ["k_pose_graph"], "loop_verify": ["k_loop_verify"], "brief": ["k_brief_filter", "k_brief_describe"],
-                  "loop_candidates": ["k_lc_candidates"]}
+                  "loop_candidates": ["k_lc_candidates"],
+                  "global_desc": ["k_gd_prep", "k_gd_conv3", "k_gd_dw3", "k_gd_pw_mfma", "k_gd_pool"]}
 
 
 class Limits(C.Structure):
@@ -127,6 +130,39 @@ LC_STATUS = ("FOUND", "NONE", "BELOW_STRONG", "TOO_MANY_WEAK", "BAD_VECTOR")
 LC_DEFAULTS = dict(weak=0.93, strong=0.95, max_num_weak=3, min_gap=20)
 
 
+class GdLayer(C.Structure):
+    _fields_ = [("op", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("stride", C.c_int), ("relu6", C.c_int), ("add_from", C.c_int)]
+
+
+class GdPrep(C.Structure):
+    _fields_ = [("out_w", C.c_int), ("out_h", C.c_int), ("mean", C.c_float * 3), ("scale", C.c_float), ("workspace_bytes", C.c_longlong)]
+
+
+GD_OPS = ("CONV3", "DW3", "PW", "AVGPOOL")
+# the reference's blobFromImage call (src/loopclosure.cpp:103-105): it subtracts 0.485 from a 0 .. 255 value
+GD_PREP_DEFAULTS = dict(out_w=224, out_h=224, mean=(0.485, 0.456, 0.406), scale=1.0 / 255.0, workspace_bytes=0)
+
+
+def gd_layer_array(layers):
+    """[(op, cin, cout, stride, relu6, add_from)] -> a ctypes array of svslam_gd_layer"""
+    arr = (GdLayer * max(len(layers), 1))()
+    for i, l in enumerate(layers):
+        arr[i] = GdLayer(*[int(v) for v in l])
+    return arr
+
+
+def gd_prep_struct(prep):
+    """None (the reference's call) or a dict over GD_PREP_DEFAULTS -> svslam_gd_prep or None"""
+    if prep is None:
+        return None
+    unknown = set(prep) - set(GD_PREP_DEFAULTS)
+    if unknown:
+        raise TypeError("global descriptor: unknown prep key(s) %s" % sorted(unknown))
+    p = dict(GD_PREP_DEFAULTS); p.update(prep)
+    return GdPrep(int(p["out_w"]), int(p["out_h"]), (C.c_float * 3)(*[float(m) for m in p["mean"]]), float(p["scale"]),
+                  int(p["workspace_bytes"]))
+
+
 class BriefJob(C.Structure):
     _fields_ = [("slot", C.c_int), ("pt_ofs", C.c_int), ("npts", C.c_int), ("n_desc", C.c_int), ("reserved", C.c_int)]
 
@@ -186,6 +222,9 @@ def load():
         L.svslam_cloud_sor_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         L.svslam_cloud_voxel_grid.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                                               C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+        L.svslam_gdesc_configure.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+        L.svslam_gdesc_describe_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.svslam_gdesc_dim.argtypes = [C.c_void_p]
         L.svslam_dev_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         L.svslam_dev_free.argtypes = [C.c_void_p, C.c_void_p]
         L.svslam_dev_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -756,6 +795,28 @@ class Context:
         ids = np.zeros(n, np.int32); rows = np.zeros((n, self._lc_dim), np.float32)
         self._chk(self.L.svslam_loopdb_read(self.h, int(stream), n, _p(ids), _p(rows)), "loopdb_read")
         return ids, rows
+
+    # ---- global image descriptor -------------------------------------------------
+    def gdesc_configure(self, layers, params, prep=None):
+        """configure the context's descriptor network (svslam_gdesc_configure).  layers: [(op, cin, cout, stride, relu6, add_from)]
+        (gdesc.mobilenet_v2_layers() is the reference's); params: the weights and biases, one f32 array in table order;
+        prep: None for the reference's call or a dict over GD_PREP_DEFAULTS"""
+        arr = gd_layer_array(layers)
+        prm = np.ascontiguousarray(params, np.float32).reshape(-1)
+        P = gd_prep_struct(prep)
+        self._chk(self.L.svslam_gdesc_configure(self.h, len(layers), C.cast(arr, C.c_void_p), _p(prm), prm.size,
+                                                C.cast(C.pointer(P), C.c_void_p) if P is not None else None), "gdesc_configure")
+
+    def gdesc_dim(self):
+        """floats per descriptor, 0 while no network is configured (svslam_gdesc_dim)"""
+        return int(self.L.svslam_gdesc_dim(self.h))
+
+    def gdesc_describe(self, slots):
+        """the raw descriptors [n, dim] f32 of level 0 of the given pyramid slots, all in one call (svslam_gdesc_describe_batch)"""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        out = np.zeros((len(sl), max(self.gdesc_dim(), 1)), np.float32)
+        self._chk(self.L.svslam_gdesc_describe_batch(self.h, len(sl), _p(sl), _p(out)), "gdesc_describe")
+        return out[:, :self.gdesc_dim()] if self.gdesc_dim() else out[:, :0]
 
     # ---- shared-map BA (one rank's shard; the LM driver is shared_ba.py) ---------
     def sba_open(self, cam_l, ext_l, cam_r, ext_r, poses, pts, okf, olm, ori, ouv, huber_delta=5.991):

@@ -9,6 +9,7 @@
                             being plain C++ between the HIP qualifiers
   lib/libbrief_host_emu.so  csrc/k_brief.h compiled for the host (tests/cpp/brief_host_emu), for the same reason
   lib/liblc_host_emu.so     csrc/k_loop_candidates.h compiled for the host (tests/cpp/lc_host_emu), for the same reason
+  lib/libgd_host_emu.so     csrc/k_global_desc.h compiled for the host (tests/cpp/gd_host_emu), for the same reason
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the build container.
 """
@@ -136,9 +137,20 @@ def build_lc_emu(force=False, verbose=False):
     return out
 
 
+def build_gd_emu(force=False, verbose=False):
+    os.makedirs(LIB, exist_ok=True)
+    out = os.path.join(LIB, "libgd_host_emu.so")
+    main = os.path.join(ROOT, "tests", "cpp", "gd_host_emu", "emu.cpp")
+    if not os.path.exists(main):
+        return None
+    if force or _newer(out, [main, os.path.join(CSRC, "k_global_desc.h")]):
+        _run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", main, "-o", out], verbose)
+    return out
+
+
 def build_all(force=False, verbose=False):
     return [build_hip(force, verbose), build_synth(force, verbose), build_pipeline(force, verbose), build_lv_emu(force, verbose),
-            build_brief_emu(force, verbose), build_lc_emu(force, verbose)]
+            build_brief_emu(force, verbose), build_lc_emu(force, verbose), build_gd_emu(force, verbose)]
 
 
 if __name__ == "__main__":

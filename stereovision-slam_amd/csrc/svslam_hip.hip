@@ -49,6 +49,7 @@ typedef enum { ncclDouble = 8 } ncclDataType_t;
 #include "k_loop_verify.h"
 #include "k_brief.h"
 #include "k_loop_candidates.h"
+#include "k_global_desc.h"
 
 #define SVSLAM_DMAP_CHUNK 512     /* keyframe jobs per svslam_dmap_keyframe_batch call the staging arena is sized for */
 #define SVSLAM_DMAP_EVICT_PER_JOB 512   /* evicted-landmark records per job of a call (shared by the call's jobs; the surplus waits) */
@@ -65,6 +66,7 @@ enum { FAM_PYR = 0, FAM_LK, FAM_GFTT, FAM_TRI, FAM_POSE, FAM_BA,
        FAM_LV,         // 14: "loop_verify", svslam_loop_verify_batch (units = jobs); appended, nothing moved
        FAM_BRIEF,      // 15: "brief", svslam_brief_describe_batch (units = points); appended, nothing moved
        FAM_LC,         // 16: "loop_candidates", svslam_loop_candidates_batch (units = rows compared); appended, nothing moved
+       FAM_GD,         // 17: "global_desc", svslam_gdesc_describe_batch (units = jobs); appended, nothing moved
        FAM_COUNT };
 
 struct Timing {
@@ -121,6 +123,10 @@ struct svslam_ctx {
     struct { unsigned char *d = nullptr; size_t cap = 0; std::vector<unsigned char> h; } br;
     // loop candidates: the resident store of normalised global descriptors (S on the device, H its bookkeeping) and a call's staging
     struct { LcStore S = {}; LcHost H; unsigned char *d = nullptr; size_t cap = 0; std::vector<unsigned char> h; } lc;
+    // global descriptor (svslam_gdesc_*): the configured network, its parameters and resize tables on the device, the workspace of a
+    // chunk of jobs and a call's slots / vectors, allocated inside the call on demand and kept
+    struct { GdNet N; float *d_prm = nullptr; int *d_tab = nullptr; float *ws = nullptr; size_t ws_cap = 0; unsigned char *io = nullptr;
+             size_t io_cap = 0; std::vector<float> h; } gd;
     // BA scratch
     BaWork bw;
     int bw_jobs = 0;          // problems per call the BA scratch holds
@@ -798,6 +804,7 @@ void svslam_destroy(svslam_ctx *c)
     (void)hipFree(c->lv.d);
     (void)hipFree(c->br.d);
     (void)hipFree(c->lc.d); (void)hipFree(c->lc.S.rows); (void)hipFree(c->lc.S.ids);
+    (void)hipFree(c->gd.d_prm); (void)hipFree(c->gd.d_tab); (void)hipFree(c->gd.ws); (void)hipFree(c->gd.io);
     ba_work_free(c->bw);
     ll_release(c);
     if (c->d_ba_prof) (void)hipFree(c->d_ba_prof);
@@ -2937,6 +2944,131 @@ int svslam_loopdb_read(svslam_ctx *c, int stream, int max_rows, int *kf_ids, flo
     HIPCHK(c, hipMemcpy(rows.data(), S.rows + at * S.dp, sizeof(float) * (size_t)n * S.dp, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(kf_ids, S.ids + at, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
     for (int r = 0; r < n; ++r) lc_unpermute(rows.data() + (size_t)r * S.dp, S.dim, S.dp, vecs + (size_t)r * S.dim);
+    return 0;
+}
+
+// ------------------------------------------------------------------ global image descriptor
+int svslam_gdesc_mobilenet_v2(svslam_gd_layer *out, int cap)
+{
+    static_assert(sizeof(svslam_gd_layer) == sizeof(GdLayer), "svslam_gd_layer is GdLayer");
+    if (cap < 0 || (cap && !out)) return -1;
+    return gd_mobilenet_v2(reinterpret_cast<GdLayer *>(out), cap);
+}
+
+int svslam_gdesc_dim(svslam_ctx *c) { return c ? c->gd.N.dim : 0; }
+
+int svslam_gdesc_configure(svslam_ctx *c, int nlayers, const svslam_gd_layer *layers, const float *params, long long nparams,
+                           const svslam_gd_prep *prep)
+{
+    if (!c) return -1;
+    static_assert(sizeof(svslam_gd_prep) == sizeof(GdPrep), "svslam_gd_prep is GdPrep");
+    if (arena_busy(c)) return -1;
+    GdNet M;
+    const char *why = nullptr;
+    try { why = gd_configure(M, c->geom.w[0], c->geom.h[0], nlayers, reinterpret_cast<const GdLayer *>(layers), params, nparams,
+                             reinterpret_cast<const GdPrep *>(prep)); }
+    catch (const std::bad_alloc &) { return fail(c, "gdesc_configure: no host memory"); }
+    if (why) return fail(c, "gdesc_configure: %s", why);
+    float *d_prm = nullptr; int *d_tab = nullptr;
+    const size_t pb = sizeof(float) * std::max(M.packed.size(), (size_t)32), tb = sizeof(int) * M.tab.size();
+    if (hipMalloc(&d_prm, pb) != hipSuccess || hipMalloc(&d_tab, tb) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(d_prm);
+        return fail(c, "gdesc_configure: no device memory for %zu bytes of parameters (the old network is kept)", pb + tb);
+    }
+    if ((M.packed.size() && hipMemcpy(d_prm, M.packed.data(), sizeof(float) * M.packed.size(), hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(d_tab, M.tab.data(), tb, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(d_prm); (void)hipFree(d_tab);
+        return fail(c, "gdesc_configure: the upload of the parameters failed (the old network is kept)");
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(c->gd.d_prm); (void)hipFree(c->gd.d_tab); (void)hipFree(c->gd.ws);
+    c->gd.d_prm = d_prm; c->gd.d_tab = d_tab; c->gd.ws = nullptr; c->gd.ws_cap = 0;
+    c->gd.N = std::move(M);
+    return 0;
+}
+
+int svslam_gdesc_describe_batch(svslam_ctx *c, int njobs, const int *slots, float *vecs)
+{
+    if (!c) return -1;
+    if (njobs < 0) return fail(c, "gdesc_describe: negative count");
+    if (njobs && (!slots || !vecs)) return fail(c, "gdesc_describe: null array");
+    if (arena_busy(c)) return -1;
+    const GdNet &N = c->gd.N;
+    const char *why = gd_check_describe(N, njobs, slots, c->lim.max_slots);
+    if (why) return fail(c, "gdesc_describe: %s", why);
+    if (njobs == 0) return 0;
+    static const bool valu = []{ const char *e = std::getenv("SVSLAM_GD_VALU"); return e && atoi(e) != 0; }();   // A/B: PW on the VALU
+    const int chunk = gd_chunk(N, njobs);
+    const size_t ws_bytes = sizeof(float) * (size_t)chunk * (size_t)N.job_floats;
+    if (ws_bytes > c->gd.ws_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(c->gd.ws); c->gd.ws = nullptr; c->gd.ws_cap = 0;
+        if (hipMalloc(&c->gd.ws, ws_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, "gdesc_describe: no device memory for %zu bytes of workspace", ws_bytes);
+        }
+        c->gd.ws_cap = ws_bytes;
+    }
+    const size_t sb = (sizeof(int) * (size_t)njobs + 255) & ~(size_t)255, vb = sizeof(float) * (size_t)njobs * N.dim;
+    if (sb + vb > c->gd.io_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(c->gd.io); c->gd.io = nullptr; c->gd.io_cap = 0;
+        const size_t want = sb + vb + (sb + vb) / 4;
+        if (hipMalloc(&c->gd.io, want) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, "gdesc_describe: no device memory for %zu bytes", want);
+        }
+        c->gd.io_cap = want;
+    }
+    try { if (c->gd.h.size() < (size_t)njobs * N.dim) c->gd.h.resize((size_t)njobs * N.dim); }
+    catch (const std::bad_alloc &) { return fail(c, "gdesc_describe: no host memory for %zu bytes of staging", vb); }
+    int *d_slots = reinterpret_cast<int *>(c->gd.io);
+    float *d_vecs = reinterpret_cast<float *>(c->gd.io + sb);
+    HIPCHK(c, hipMemcpyAsync(d_slots, slots, sizeof(int) * (size_t)njobs, hipMemcpyHostToDevice, c->stream));
+    const PyrGeom &g = c->geom;
+    GdPrepArgs PA;
+    PA.I.base = c->d_pyr; PA.I.slot_bytes = g.slot_bytes; PA.I.origin = g.ofs[0] + (size_t)SVS_BORDER * g.pitch[0] + SVS_BORDER;
+    PA.I.pitch = g.pitch[0]; PA.I.w = g.w[0]; PA.I.h = g.h[0];
+    PA.tab = c->gd.d_tab; PA.ws = c->gd.ws; PA.u8 = nullptr; PA.job_floats = N.job_floats; PA.out_w = N.prep.out_w; PA.out_h = N.prep.out_h;
+    for (int k = 0; k < 3; ++k) PA.mean[k] = N.prep.mean[k];
+    PA.scale = N.prep.scale;
+    tm_begin(c, FAM_GD, njobs);
+    for (int j0 = 0; j0 < njobs; j0 += chunk) {
+        const int nj = std::min(chunk, njobs - j0);
+        PA.slots = d_slots + j0; PA.njobs = nj;
+        hipLaunchKernelGGL(k_gd_prep, dim3(cdiv(PA.out_w * PA.out_h, GD_THREADS), nj), dim3(GD_THREADS), 0, c->stream, PA);
+        for (const GdL &L : N.L) {
+            GdArgs A;
+            A.L = L; A.prm = c->gd.d_prm; A.ws = c->gd.ws; A.vecs = d_vecs + (size_t)j0 * N.dim; A.job_floats = N.job_floats; A.njobs = nj;
+            const long long hw = (long long)L.hout * L.wout, elems = hw * L.cout;
+            if (L.op == GD_CONV3)
+                hipLaunchKernelGGL(k_gd_conv3, dim3((unsigned)((hw + GD_THREADS - 1) / GD_THREADS), L.cout, nj), dim3(GD_THREADS), 0, c->stream, A);
+            else if (L.op == GD_DW3)
+                hipLaunchKernelGGL(k_gd_dw3, dim3((unsigned)((elems + GD_THREADS - 1) / GD_THREADS), nj), dim3(GD_THREADS), 0, c->stream, A);
+            else if (L.op == GD_PW && valu)
+                hipLaunchKernelGGL(k_gd_pw, dim3((unsigned)((elems + GD_THREADS - 1) / GD_THREADS), nj), dim3(GD_THREADS), 0, c->stream, A);
+            else if (L.op == GD_PW) {
+                // channel tiles per wave: four while that leaves 2048 waves (two per SIMD of the chip's 256 CUs), else fewer
+                const long long ptiles = (hw * nj + 31) / 32;
+                const int ct = L.coutp / 32;
+                int NT = 4;
+                while (NT > 1 && ptiles * cdiv(ct, NT) < 2048) NT >>= 1;
+                const dim3 grid((unsigned)((ptiles + 3) / 4), cdiv(ct, NT));
+                if (NT == 4) hipLaunchKernelGGL(k_gd_pw_mfma<4>, grid, dim3(GD_THREADS), 0, c->stream, A);
+                else if (NT == 2) hipLaunchKernelGGL(k_gd_pw_mfma<2>, grid, dim3(GD_THREADS), 0, c->stream, A);
+                else hipLaunchKernelGGL(k_gd_pw_mfma<1>, grid, dim3(GD_THREADS), 0, c->stream, A);
+            }
+            else
+                hipLaunchKernelGGL(k_gd_pool, dim3(cdiv(L.cout, GD_THREADS), nj), dim3(GD_THREADS), 0, c->stream, A);
+        }
+    }
+    tm_end(c);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->gd.h.data(), d_vecs, vb, hipMemcpyDeviceToHost, c->stream));
+    if (d2h_sync(c, 0, 0)) return -1;
+    memcpy(vecs, c->gd.h.data(), vb);
     return 0;
 }
 

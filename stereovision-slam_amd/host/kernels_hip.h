@@ -122,6 +122,11 @@ public:
     int brief_describe(int n, svslam_brief_job *jobs, const svslam_brief_params *prm, int total_pts, const float *xy, uint8_t *desc, int *desc_pt)
     { return svslam_brief_describe_batch(ctx_, n, jobs, prm, total_pts, xy, desc, desc_pt); }
 
+    int gdesc_configure(int nlayers, const svslam_gd_layer *layers, const float *params, long long nparams, const svslam_gd_prep *prep)
+    { return svslam_gdesc_configure(ctx_, nlayers, layers, params, nparams, prep); }
+    int gdesc_describe(int n, const int *slots, float *vecs) { return svslam_gdesc_describe_batch(ctx_, n, slots, vecs); }
+    int gdesc_dim() { return svslam_gdesc_dim(ctx_); }
+
     int loopdb_configure(int nstreams, int capacity, int dim) { return svslam_loopdb_configure(ctx_, nstreams, capacity, dim); }
     int loopdb_append(int n, const int *streams, const int *kf_ids, const float *vecs) { return svslam_loopdb_append_batch(ctx_, n, streams, kf_ids, vecs); }
     int loop_candidates(int n, svslam_lc_job *jobs, const svslam_lc_params *prm, const float *vecs) { return svslam_loop_candidates_batch(ctx_, n, jobs, prm, vecs); }

@@ -176,7 +176,7 @@ extern "C" int svs_pipe_detect_loops(void *p, const float *vecs, const svs_loop_
 {
     typedef svs::Pipeline<SVS_PIPE_KERNELS> Pipe;
     PipeHandle *h = static_cast<PipeHandle *>(p);
-    if (!vecs || !dp || !loop_params || !results) { g_err = "svs_pipe_detect_loops: null argument"; return -1; }
+    if (!dp || !loop_params || !results) { g_err = "svs_pipe_detect_loops: null argument"; return -1; }     // vecs == NULL: the configured network
     try {
         Pipe::LoopDetectParams P;
         P.cand.weak = dp->weak; P.cand.strong = dp->strong; P.cand.max_num_weak = dp->max_num_weak; P.cand.min_gap = dp->min_gap;
@@ -198,6 +198,35 @@ extern "C" int svs_pipe_detect_loops(void *p, const float *vecs, const svs_loop_
             std::memcpy(o.loop.T_corr, R.T_corr.v, 56); std::memcpy(o.loop.T_rel, R.T_rel.v, 56); o.loop.d = R.d;
         }
         return 0;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+// Global image descriptor (product build only: the CPU twins' providers have no gdesc_describe)
+extern "C" int svs_pipe_gdesc_configure(void *p, int nlayers, const void *layers, const float *params, long long nparams, const void *prep_or_null)
+{
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    try {
+        if (!h->pipe->ConfigureGlobalDescriptor(nlayers, static_cast<const svslam_gd_layer *>(layers), params, nparams,
+                                                static_cast<const svslam_gd_prep *>(prep_or_null))) { g_err = h->pipe->last_error(); return -1; }
+        return 0;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+extern "C" int svs_pipe_gdesc_dim(void *p) { return static_cast<PipeHandle *>(p)->pipe->GlobalDescriptorDim(); }
+extern "C" int svs_pipe_describe_global_new_keyframes(void *p, float *vecs)
+{
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    if (!vecs) { g_err = "svs_pipe_describe_global_new_keyframes: null argument"; return -1; }
+    try {
+        std::vector<float> v;
+        int n = 0;
+        if (!h->pipe->DescribeGlobalNewKeyframes(&v, &n)) { g_err = h->pipe->last_error(); return -1; }
+        if (!v.empty()) std::memcpy(vecs, v.data(), sizeof(float) * v.size());
+        return n;
     } catch (const std::exception &e) {
         g_err = e.what();
         return -1;

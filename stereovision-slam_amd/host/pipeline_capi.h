@@ -125,7 +125,8 @@ int svs_pipe_loopdb_configure(void *p, int capacity, int dim);
  * svslam_loop_params (cam and ext_l are filled in by the pipeline).  results: [nstreams]; cand_status and loop.status are -1 where that
  * stage did not run.  The matches of a verified stream: svs_pipe_loop_matches.  -1 (svs_pipe_last_error, nothing done): device_map =
  * 1, a store that was not configured, a new keyframe that was never described, a full stream, a kernel's refusal.  LocalFusion is the
- * caller's. */
+ * caller's.  vecs == NULL: the vectors come from the network svs_pipe_gdesc_configure set, computed here for the keyframes this call
+ * handles; refused when no network is configured or when the store's dim is not the network's. */
 typedef struct svs_loop_detect_params { float weak, strong; int max_num_weak, min_gap; long long keyframes_to_ignore_after_loop; } svs_loop_detect_params;
 typedef struct svs_loop_detection {
     int is_keyframe, skipped, searched, verified, stored, reserved;
@@ -134,6 +135,16 @@ typedef struct svs_loop_detection {
     svs_loop_result loop;
 } svs_loop_detection;
 int svs_pipe_detect_loops(void *p, const float *vecs, const svs_loop_detect_params *dp, const void *loop_params, svs_loop_detection *results);
+/* The network behind the global image descriptor (svslam_gdesc_configure): layers is svslam_gd_layer [nlayers], params the
+ * weights and biases in table order, prep_or_null svslam_gd_prep or NULL for the reference's call.  -1: the kernel's refusal, the
+ * network configured before is kept.  svs_pipe_gdesc_dim: floats per descriptor, 0 while none is configured.  Product library only. */
+int svs_pipe_gdesc_configure(void *p, int nlayers, const void *layers, const float *params, long long nparams, const void *prep_or_null);
+int svs_pipe_gdesc_dim(void *p);
+/* LoopClosure::ExtractFeatureVec (src/loopclosure.cpp:92-129) for every stream whose last step made a keyframe, on the keyframe's left
+ * image (level 0 of its pyramid slot, until the stream's next step); one kernel call for all streams.  vecs: [nstreams][dim], raw; the
+ * rows of the other streams are zeroed.  Works with device_map = 1 as well.  Returns the number of rows computed, -1 (nothing
+ * written): no network configured, the kernel's refusal. */
+int svs_pipe_describe_global_new_keyframes(void *p, float *vecs);
 /* the matches (candidate row, current row, distance, inlier) of the pair the last svs_pipe_detect_loops verified on a stream: returns
  * their number (nothing written when cap is smaller or match4 is NULL), -1 when it verified none there */
 long long svs_pipe_loop_matches(void *p, int stream, int *match4, long long cap);

@@ -276,6 +276,10 @@ struct FrontendOptions {            // the hyper-parameters Frontend::Frontend()
     // Frontend::DetectLoop's store of global descriptors: `loop_store_capacity` keyframes of `loop_descriptor_dim` floats (the
     // reference's vector has 1280); allocated at the first DetectLoop, never without it
     int loop_store_capacity = 4096, loop_descriptor_dim = 1280;
+    // `loop_global_descriptor: <file>` in the YAML (or this field): a file written by gdesc.save (magic, version, layer table, prep,
+    // parameters) that configures the network behind the global image descriptor at start (Pipeline::ConfigureGlobalDescriptor);
+    // DetectLoop(out) then needs no vector from the caller and loop_descriptor_dim becomes the network's.  Empty (default): no network.
+    std::string loop_global_descriptor;
     static FrontendOptions FromConfig(const ConfigFile &c)
     {
         FrontendOptions o;
@@ -285,6 +289,7 @@ struct FrontendOptions {            // the hyper-parameters Frontend::Frontend()
         o.loop_descriptors = (int)c.Num("loop_descriptors", o.loop_descriptors);
         o.loop_store_capacity = (int)c.Num("loop_store_capacity", o.loop_store_capacity);
         o.loop_descriptor_dim = (int)c.Num("loop_descriptor_dim", o.loop_descriptor_dim);
+        o.loop_global_descriptor = c.Str("loop_global_descriptor", "");
         o.num_features = (int)c.Num("num_features", o.num_features);
         o.num_features_init = (int)c.Num("num_features_init", o.num_features_init);
         o.num_features_tracking = (int)c.Num("num_features_tracking", o.num_features_tracking);
@@ -304,6 +309,41 @@ template <class K> constexpr bool provider_has_device_map(long) { return false; 
 // does it offer the descriptor kernel (HipKernels::brief_describe)?  The providers of the CPU twins do not.
 template <class K> constexpr auto provider_has_brief(int) -> decltype(&K::brief_describe, true) { return true; }
 template <class K> constexpr bool provider_has_brief(long) { return false; }
+// does it offer the global-descriptor network (HipKernels::gdesc_describe)?
+template <class K> constexpr auto provider_has_gdesc(int) -> decltype(&K::gdesc_describe, true) { return true; }
+template <class K> constexpr bool provider_has_gdesc(long) { return false; }
+
+// A file written by gdesc.save, little-endian: "SVGD", u32 version = 1, u32 nlayers, nlayers x 6 i32, i32 out_w, i32 out_h, 3 f32 mean,
+// f32 scale, i64 workspace_bytes, i64 nparams, nparams f32.  Throws SLAMException on a file that is not one.
+struct GlobalDescriptorFile {
+    std::vector<svslam_gd_layer> layers;
+    std::vector<float> params;
+    svslam_gd_prep prep;
+    explicit GlobalDescriptorFile(const std::string &path)
+    {
+        std::ifstream f(path, std::ios::binary);
+        if (!f) throw SLAMException("loop_global_descriptor: cannot open " + path);
+        std::vector<char> raw((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        size_t o = 0;
+        auto take = [&](void *dst, size_t n) {
+            if (o + n > raw.size()) throw SLAMException("loop_global_descriptor: " + path + " is truncated");
+            std::memcpy(dst, raw.data() + o, n); o += n;
+        };
+        char magic[4]; uint32_t ver = 0, n = 0;
+        take(magic, 4); take(&ver, 4); take(&n, 4);
+        if (std::memcmp(magic, "SVGD", 4) != 0 || ver != 1 || n > 4096) throw SLAMException("loop_global_descriptor: " + path + " is not a version-1 descriptor file");
+        layers.resize(n);
+        for (uint32_t i = 0; i < n; ++i) { int32_t v[6]; take(v, 24); layers[i] = svslam_gd_layer{ v[0], v[1], v[2], v[3], v[4], v[5] }; }
+        int32_t wh[2]; float ms[4]; int64_t ws = 0, np = 0;
+        take(wh, 8); take(ms, 16); take(&ws, 8); take(&np, 8);
+        std::memset(&prep, 0, sizeof(prep));
+        prep.out_w = wh[0]; prep.out_h = wh[1]; prep.mean[0] = ms[0]; prep.mean[1] = ms[1]; prep.mean[2] = ms[2]; prep.scale = ms[3];
+        prep.workspace_bytes = (long long)ws;
+        if (np < 0 || (uint64_t)np * 4 != raw.size() - o) throw SLAMException("loop_global_descriptor: " + path + " does not hold the parameters its header counts");
+        params.resize((size_t)np);
+        if (np) take(params.data(), (size_t)np * 4);
+    }
+};
 
 template <class K>
 class FrontendT {
@@ -400,6 +440,14 @@ public:
         if (out) *out = res[0];
         return true;
     }
+    // the same with the vector computed by the network of `loop_global_descriptor` (LoopClosure::ExtractFeatureVec on the keyframe's
+    // left image): a loop is closed from the frames alone.  Throws without the key, the way DetectLoop does without `loop_descriptors`.
+    bool DetectLoop(const typename Pipeline<K>::LoopDetectParams &params, typename Pipeline<K>::LoopDetection *out)
+    {
+        if (!pipe_) return false;
+        if (opt_.loop_global_descriptor.empty()) throw SLAMException("DetectLoop without a vector needs loop_global_descriptor: <file> in the configuration");
+        return DetectLoop(nullptr, params, out);
+    }
     K *kernels() { return kernels_.get(); }
     bool LowLatency() const { return opt_.low_latency != 0; }
 
@@ -411,6 +459,18 @@ private:
             if (!pipe_->DescribeNewKeyframes()) throw SLAMException(pipe_->last_error());
         } else {
             throw SLAMException("loop_descriptors: this kernel provider has no descriptor kernel");
+        }
+    }
+    // (a function of its own so that a provider without the kernels never instantiates Pipeline::ConfigureGlobalDescriptor)
+    void configure_global_descriptor()
+    {
+        if constexpr (provider_has_gdesc<K>(0)) {
+            const GlobalDescriptorFile F(opt_.loop_global_descriptor);
+            if (!pipe_->ConfigureGlobalDescriptor((int)F.layers.size(), F.layers.data(), F.params.data(), (long long)F.params.size(), &F.prep))
+                throw SLAMException(pipe_->last_error());
+            opt_.loop_descriptor_dim = pipe_->GlobalDescriptorDim();
+        } else {
+            throw SLAMException("loop_global_descriptor: this kernel provider has no descriptor network");
         }
     }
     void create(int w, int h)
@@ -444,6 +504,7 @@ private:
         if (kernels_->set_pose_only_xtol(opt_.pose_xtol) != 0) throw SLAMException(std::string("pose_xtol: ") + kernels_->last_error());
         pipe_.reset(new Pipeline<K>(cfg, *kernels_, 1, 1));
         if (opt_.loop_descriptors) pipe_->SetKeepKeyframeFeatures(true);
+        if (!opt_.loop_global_descriptor.empty()) configure_global_descriptor();
         wire_backend(); wire_map();
     }
     void unwire()
@@ -636,8 +697,10 @@ public:
         p.cand.min_gap = (int)config_.Num("loop_min_keyframe_gap", 20);
         p.verify = loop_params(seed);
         p.keyframes_to_ignore_after_loop = (long)config_.Num("keyframes_to_ignore_after_loop", 5);
-        return frontend_->DetectLoop(vec, p, out);
+        return vec ? frontend_->DetectLoop(vec, p, out) : frontend_->DetectLoop(p, out);
     }
+    // the same from the frames alone: the vector is the configured network's (`loop_global_descriptor: <file>`); throws without the key
+    bool DetectLoop(typename Pipeline<K>::LoopDetection *out, unsigned seed = 0) { return DetectLoop(nullptr, out, seed); }
     FrontendStatus GetFrontendStatus() const { return frontend_->GetStatus(); }
     // keyframes.txt + landmarks.pcd under output_dir (:198-310; the reference adds a time-stamped folder)
     bool saveSLAMOutputInFile(const std::string &dir_override = "")

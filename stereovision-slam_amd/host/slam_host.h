@@ -896,6 +896,22 @@ public:
         }
         return VerifyLoops(qs, params, results);
     }
+    // The network behind the global image descriptor (svslam_gdesc_configure): a table of layers, its parameters and the
+    // preprocessing (nullptr: the reference's call).  Replaces the network configured before; a refusal keeps that one.
+    bool ConfigureGlobalDescriptor(int nlayers, const svslam_gd_layer *layers, const float *params, long long nparams, const svslam_gd_prep *prep = nullptr)
+    {
+        Flush();
+        if (k_.gdesc_configure(nlayers, layers, params, nparams, prep) != 0) return refuse(std::string("ConfigureGlobalDescriptor: ") + k_.last_error());
+        gd_dim_ = k_.gdesc_dim();
+        return true;
+    }
+    int GlobalDescriptorDim() const { return gd_dim_; }
+    // LoopClosure::ExtractFeatureVec (src/loopclosure.cpp:92-129) for every stream whose last step made a keyframe: the configured
+    // network on level 0 of slot_cur, where the keyframe's left image still is until the stream's next step (the window of
+    // DescribeNewKeyframes).  ONE provider call for all streams.  vecs becomes [nstreams][dim], raw; the rows of the other streams
+    // are zero.  The kernels read only the image, so this works with device_map = 1 as well.  n_described (optional): rows
+    // computed.  False (last_error(), vecs untouched): no network configured, the provider's refusal.
+    bool DescribeGlobalNewKeyframes(std::vector<float> *vecs, int *n_described = nullptr) { return DescribeGlobal(vecs, n_described, false); }
     // The store of global image descriptors DetectLoops searches (svslam_loopdb_configure): capacity rows of dim floats
     // for every stream, emptied.  Every stream's last_closed is forgotten with it.
     bool ConfigureLoopStore(int capacity, int dim)
@@ -918,6 +934,8 @@ public:
     // (:858) is not done: the result carries the LoopResult for it.  A keyframe is handled once: a second call after the same step
     // finds nothing to do.  False (last_error(), nothing done): device_map = 1, a store that was not configured, a new keyframe
     // that was never described, a stream whose store is full, the provider's refusal.
+    // vecs == nullptr: the vectors are computed here by the configured network (ConfigureGlobalDescriptor), for the keyframes this
+    // call handles; refused when no network is configured, or when the store's dim is not the network's.
     struct LoopDetectParams { svslam_lc_params cand; svslam_loop_params verify; long keyframes_to_ignore_after_loop; };
     struct LoopDetection {
         bool is_keyframe = false, skipped = false, searched = false, verified = false, stored = false;
@@ -929,7 +947,13 @@ public:
     {
         if (device_map()) return refuse("DetectLoops: with device_map = 1 the keyframes' features live on the device; not supported yet");
         if (lc_dim_ == 0) return refuse("DetectLoops: the store was not configured (ConfigureLoopStore)");
-        if (!vecs) return refuse("DetectLoops: null descriptors");
+        std::vector<float> own;
+        if (!vecs) {
+            if (gd_dim_ == 0) return refuse("DetectLoops: no descriptors were given and no network is configured (ConfigureGlobalDescriptor)");
+            if (gd_dim_ != lc_dim_) return refuse("DetectLoops: the store's dim is not the configured network's");
+            if (!DescribeGlobal(&own, nullptr, true)) return false;
+            vecs = own.data();
+        }
         const int ns = nstreams();
         std::vector<LoopDetection> out((size_t)ns);
         std::vector<Frame *> fresh((size_t)ns, nullptr);
@@ -996,6 +1020,29 @@ public:
 private:
     bool refuse(const std::string &why) { refusal_ = why; return false; }
     std::string refusal_;
+    int gd_dim_ = 0;               // floats per global descriptor of the configured network (0: none)
+    // unchecked_only: the keyframes DetectLoops has not handled yet
+    bool DescribeGlobal(std::vector<float> *vecs, int *n_described, bool unchecked_only)
+    {
+        if (n_described) *n_described = 0;
+        if (!vecs) return refuse("DescribeGlobalNewKeyframes: null output");
+        if (gd_dim_ == 0) return refuse("DescribeGlobalNewKeyframes: no network is configured (ConfigureGlobalDescriptor)");
+        Flush();
+        std::vector<int> slots, who;
+        for (int s = 0; s < nstreams(); ++s) {
+            const Frame *f = streams_[s]->last;
+            if (!f || !f->is_keyframe || (unchecked_only && f->loop_checked)) continue;
+            slots.push_back(streams_[s]->slot_cur); who.push_back(s);
+        }
+        std::vector<float> rows(slots.size() * (size_t)gd_dim_ + 1);
+        if (!slots.empty() && k_.gdesc_describe((int)slots.size(), slots.data(), rows.data()) != 0)
+            return refuse(std::string("DescribeGlobalNewKeyframes: ") + k_.last_error());
+        vecs->assign((size_t)nstreams() * (size_t)gd_dim_, 0.f);
+        for (size_t j = 0; j < who.size(); ++j)
+            std::memcpy(vecs->data() + (size_t)who[j] * gd_dim_, rows.data() + j * (size_t)gd_dim_, sizeof(float) * (size_t)gd_dim_);
+        if (n_described) *n_described = (int)who.size();
+        return true;
+    }
     // DetectLoops: the store's shape (0: not configured), the keyframe that last closed a loop per stream (-1: none), the last results
     int lc_dim_ = 0, lc_capacity_ = 0;
     std::vector<long> lc_last_closed_;

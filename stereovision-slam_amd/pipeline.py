@@ -144,6 +144,10 @@ def _bind(L):
         L.svs_pipe_loopdb_configure.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.svs_pipe_detect_loops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.svs_pipe_loop_matches.restype = C.c_longlong
+        if hasattr(L, "svs_pipe_gdesc_configure"):
+            L.svs_pipe_gdesc_configure.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+            L.svs_pipe_gdesc_dim.argtypes = [C.c_void_p]
+            L.svs_pipe_describe_global_new_keyframes.argtypes = [C.c_void_p, C.c_void_p]
         L.svs_pipe_loop_matches.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
         L.svs_pipe_loopdb_ids.restype = C.c_longlong
         L.svs_pipe_loopdb_ids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
@@ -374,10 +378,36 @@ class Pipeline:
             raise RuntimeError("svs_pipe_loopdb_configure refused: " + self.L.svs_pipe_last_error().decode())
         self._lc_dim = int(dim)
 
-    def detect_loops(self, vecs, keyframes_to_ignore_after_loop=5, weak=None, strong=None, max_num_weak=None, min_gap=None, **loop_params):
+    def configure_global_descriptor(self, layers, params, prep=None):
+        """the network behind the global image descriptor (svs_pipe_gdesc_configure): layers as Context.gdesc_configure
+        (gdesc.mobilenet_v2_layers() is the reference's), params one f32 array in table order, prep None for the reference's call or a
+        dict over GD_PREP_DEFAULTS.  With a network configured detect_loops needs no vecs."""
+        import importlib
+        _svs = importlib.import_module(__package__)
+        arr = _svs.gd_layer_array(layers)
+        prm = np.ascontiguousarray(params, np.float32).reshape(-1)
+        P = _svs.gd_prep_struct(prep)
+        if self.L.svs_pipe_gdesc_configure(self.h, len(layers), C.cast(arr, C.c_void_p), prm.ctypes.data_as(C.c_void_p), prm.size,
+                                           C.cast(C.pointer(P), C.c_void_p) if P is not None else None) != 0:
+            raise RuntimeError("svs_pipe_gdesc_configure refused: " + self.L.svs_pipe_last_error().decode())
+
+    def global_descriptor_dim(self):
+        return int(self.L.svs_pipe_gdesc_dim(self.h))
+
+    def describe_global_new_keyframes(self):
+        """LoopClosure::ExtractFeatureVec for every stream whose last step made a keyframe (svs_pipe_describe_global_new_keyframes):
+        (vecs [nstreams, dim] raw, rows of the other streams zero; the number of rows computed).  Works with device_map = 1."""
+        v = np.zeros((self.n, max(self.global_descriptor_dim(), 1)), np.float32)
+        n = self.L.svs_pipe_describe_global_new_keyframes(self.h, v.ctypes.data_as(C.c_void_p))
+        if n < 0:
+            raise RuntimeError("svs_pipe_describe_global_new_keyframes refused: " + self.L.svs_pipe_last_error().decode())
+        return v, n
+
+    def detect_loops(self, vecs=None, keyframes_to_ignore_after_loop=5, weak=None, strong=None, max_num_weak=None, min_gap=None, **loop_params):
         """LoopClosure::AddNewKeyFrame + one turn of LoopClosurePipeline for every stream whose last step made a keyframe
         (svs_pipe_detect_loops), after describe_new_keyframes: skip rule, candidate search, verification, loop edge, store update.
-        vecs: [nstreams, dim] global descriptors (rows of streams without a new keyframe are not read).  weak, strong, max_num_weak,
+        vecs: [nstreams, dim] global descriptors (rows of streams without a new keyframe are not read), or None: the network set by
+        configure_global_descriptor computes them.  weak, strong, max_num_weak,
         min_gap: LC_DEFAULTS; loop_params: as verify_loops.  Returns one dict per stream: is_keyframe, skipped, searched, verified,
         stored, kf_id, cand (status, cand_kf, best_sim, best_kf, n_weak, n_compared) or None, loop (as verify_loops) or None."""
         import importlib
@@ -389,13 +419,13 @@ class Pipeline:
         c = dict(_svs.LC_DEFAULTS)
         c.update({k: v for k, v in dict(weak=weak, strong=strong, max_num_weak=max_num_weak, min_gap=min_gap).items() if v is not None})
         ns = self.n
-        v = np.ascontiguousarray(vecs, np.float32).reshape(ns, getattr(self, "_lc_dim", -1))     # unconfigured: the library refuses
+        v = None if vecs is None else np.ascontiguousarray(vecs, np.float32).reshape(ns, getattr(self, "_lc_dim", -1))     # unconfigured: the library refuses
         D = LoopDetectParams(float(c["weak"]), float(c["strong"]), int(c["max_num_weak"]), int(c["min_gap"]), int(keyframes_to_ignore_after_loop))
         P = _svs.LoopParams((C.c_double * 4)(), (C.c_double * 7)(), int(p["min_matches"]), int(p["ransac_iters"]), float(p["reproj_px"]),
                             float(p["max_pose_distance"]), float(p["min_pose_difference"]), float(p["max_pose_difference"]),
                             int(p["seed"]) & 0xFFFFFFFF, 0)
         res = (LoopDetection * ns)()
-        if self.L.svs_pipe_detect_loops(self.h, v.ctypes.data_as(C.c_void_p), C.byref(D), C.byref(P), res) != 0:
+        if self.L.svs_pipe_detect_loops(self.h, v.ctypes.data_as(C.c_void_p) if v is not None else None, C.byref(D), C.byref(P), res) != 0:
             raise RuntimeError("svs_pipe_detect_loops refused: " + self.L.svs_pipe_last_error().decode())
         out = []
         for s in range(ns):

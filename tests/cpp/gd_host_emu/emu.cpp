@@ -1,0 +1,79 @@
+// csrc/k_global_desc.h compiled for the host (tests/test_host_emulation_global_desc.py): with GD_HOST_EMU the HIP qualifiers vanish, fmaf is
+// std::fmaf and an element function of a kernel is called in a loop over the elements the kernel's threads take (no element reads
+// what another element of the same layer writes, so the order does not matter).  The checks, the parameter packing, the buffer plan,
+// the resize tables, the chunking and every element function are the library's own code; only the launches and the copies are restated
+// here.  The images are tight: slot s is imgs + s * w * h.  The network is kept between calls, as the context keeps it.
+#define GD_HOST_EMU
+#include "../../../stereovision-slam_amd/csrc/k_global_desc.h"
+#include <string>
+
+static std::string g_gd_err;
+static GdNet g_gd_net;
+
+extern "C" const char *emu_gd_error() { return g_gd_err.c_str(); }
+
+extern "C" int emu_gd_mobilenet_v2(GdLayer *out, int cap) { return gd_mobilenet_v2(out, cap); }
+
+extern "C" int emu_gd_configure(int src_w, int src_h, int nlayers, const GdLayer *layers, const float *params, long long nparams, const GdPrep *prep)
+{
+    GdNet M;
+    const char *why = gd_configure(M, src_w, src_h, nlayers, layers, params, nparams, prep);
+    if (why) { g_gd_err = why; return -1; }
+    g_gd_net = std::move(M);
+    return 0;
+}
+
+extern "C" int emu_gd_dim() { return g_gd_net.dim; }
+
+extern "C" long long emu_gd_job_floats() { return g_gd_net.job_floats; }
+
+extern "C" int emu_gd_chunk(int njobs) { return g_gd_net.dim ? gd_chunk(g_gd_net, njobs) : 0; }
+
+// u8: the resized image [njobs][out_h][out_w] or null; blob: [njobs][3][out_h][out_w] or null; dump: the output of layer dump_layer,
+// [njobs][cout][hout][wout], or null
+extern "C" int emu_gd_describe(int nslots, const uint8_t *imgs, int njobs, const int *slots, float *vecs, uint8_t *u8, float *blob, int dump_layer,
+                               float *dump)
+{
+    const GdNet &N = g_gd_net;
+    const char *why = gd_check_describe(N, njobs, slots, nslots);
+    if (why) { g_gd_err = why; return -1; }
+    if (njobs == 0) return 0;
+    const int chunk = gd_chunk(N, njobs);
+    std::vector<float> ws((size_t)chunk * (size_t)N.job_floats);
+    std::vector<float> out((size_t)njobs * N.dim);
+    GdPrepArgs PA;
+    PA.I.base = imgs; PA.I.slot_bytes = (size_t)N.src_w * N.src_h; PA.I.origin = 0; PA.I.pitch = N.src_w; PA.I.w = N.src_w; PA.I.h = N.src_h;
+    PA.tab = N.tab.data(); PA.ws = ws.data(); PA.job_floats = N.job_floats; PA.out_w = N.prep.out_w; PA.out_h = N.prep.out_h;
+    for (int k = 0; k < 3; ++k) PA.mean[k] = N.prep.mean[k];
+    PA.scale = N.prep.scale;
+    const size_t plane = (size_t)PA.out_w * PA.out_h;
+    for (int j0 = 0; j0 < njobs; j0 += chunk) {
+        const int nj = chunk < njobs - j0 ? chunk : njobs - j0;
+        memset(ws.data(), 0xA5, ws.size() * sizeof(float));       // what the workspace holds before a chunk is not specified
+        PA.slots = slots + j0; PA.njobs = nj; PA.u8 = u8 ? u8 + (size_t)j0 * plane : nullptr;
+        for (int j = 0; j < nj; ++j)
+            for (int oy = 0; oy < PA.out_h; ++oy)
+                for (int ox = 0; ox < PA.out_w; ++ox) gd_prep_elem(PA, j, oy, ox);
+        if (blob)
+            for (int j = 0; j < nj; ++j) memcpy(blob + (size_t)(j0 + j) * 3 * plane, ws.data() + (size_t)j * N.job_floats, sizeof(float) * 3 * plane);
+        for (size_t li = 0; li < N.L.size(); ++li) {
+            GdArgs A;
+            A.L = N.L[li]; A.prm = N.packed.data(); A.ws = ws.data(); A.vecs = out.data() + (size_t)j0 * N.dim; A.job_floats = N.job_floats; A.njobs = nj;
+            const GdL &L = A.L;
+            const int hw = L.hout * L.wout;
+            for (int j = 0; j < nj; ++j) {
+                if (L.op == GD_AVGPOOL) { for (int c = 0; c < L.cout; ++c) gd_pool_elem(A, j, c); continue; }
+                for (int co = 0; co < L.cout; ++co)
+                    for (int pix = 0; pix < hw; ++pix) {
+                        if (L.op == GD_CONV3) gd_conv3_elem(A, j, co, pix);
+                        else if (L.op == GD_DW3) gd_dw3_elem(A, j, co, pix);
+                        else gd_pw_elem(A, j, co, pix);
+                    }
+                if (dump && (int)li == dump_layer)
+                    memcpy(dump + (size_t)(j0 + j) * L.cout * hw, ws.data() + (size_t)j * N.job_floats + L.out, sizeof(float) * (size_t)L.cout * hw);
+            }
+        }
+    }
+    memcpy(vecs, out.data(), sizeof(float) * out.size());
+    return 0;
+}
