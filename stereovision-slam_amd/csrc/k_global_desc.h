@@ -267,6 +267,17 @@ static inline int gd_chunk(const GdNet &N, int njobs)
     return n < njobs ? (int)n : njobs;
 }
 
+// k_gd_pw_mfma's channel tiles per wave for a PW layer of hw pixels per job over the nj jobs of a chunk: four while that leaves 2048
+// waves (two per SIMD of the chip's 256 CUs), else fewer
+static inline int gd_pw_tiles(long long hw, int nj, int coutp)
+{
+    const long long ptiles = (hw * nj + 31) / 32;
+    const int ct = coutp / 32;
+    int NT = 4;
+    while (NT > 1 && ptiles * ((ct + NT - 1) / NT) < 2048) NT >>= 1;
+    return NT;
+}
+
 static inline const char *gd_check_describe(const GdNet &N, int njobs, const int *slots, int nslots)
 {
     if (N.dim == 0) return "no network is configured";

@@ -3050,12 +3050,9 @@ int svslam_gdesc_describe_batch(svslam_ctx *c, int njobs, const int *slots, floa
             else if (L.op == GD_PW && valu)
                 hipLaunchKernelGGL(k_gd_pw, dim3((unsigned)((elems + GD_THREADS - 1) / GD_THREADS), nj), dim3(GD_THREADS), 0, c->stream, A);
             else if (L.op == GD_PW) {
-                // channel tiles per wave: four while that leaves 2048 waves (two per SIMD of the chip's 256 CUs), else fewer
                 const long long ptiles = (hw * nj + 31) / 32;
-                const int ct = L.coutp / 32;
-                int NT = 4;
-                while (NT > 1 && ptiles * cdiv(ct, NT) < 2048) NT >>= 1;
-                const dim3 grid((unsigned)((ptiles + 3) / 4), cdiv(ct, NT));
+                const int NT = gd_pw_tiles(hw, nj, L.coutp);
+                const dim3 grid((unsigned)((ptiles + 3) / 4), cdiv(L.coutp / 32, NT));
                 if (NT == 4) hipLaunchKernelGGL(k_gd_pw_mfma<4>, grid, dim3(GD_THREADS), 0, c->stream, A);
                 else if (NT == 2) hipLaunchKernelGGL(k_gd_pw_mfma<2>, grid, dim3(GD_THREADS), 0, c->stream, A);
                 else hipLaunchKernelGGL(k_gd_pw_mfma<1>, grid, dim3(GD_THREADS), 0, c->stream, A);

@@ -29,6 +29,9 @@ extern "C" long long emu_gd_job_floats() { return g_gd_net.job_floats; }
 
 extern "C" int emu_gd_chunk(int njobs) { return g_gd_net.dim ? gd_chunk(g_gd_net, njobs) : 0; }
 
+// the launcher's choice of k_gd_pw_mfma<NT> for a PW layer (hw pixels per job, nj jobs in the chunk, coutp = cout rounded up to 32)
+extern "C" int emu_gd_pw_tiles(long long hw, int nj, int coutp) { return gd_pw_tiles(hw, nj, coutp); }
+
 // u8: the resized image [njobs][out_h][out_w] or null; blob: [njobs][3][out_h][out_w] or null; dump: the output of layer dump_layer,
 // [njobs][cout][hout][wout], or null
 extern "C" int emu_gd_describe(int nslots, const uint8_t *imgs, int njobs, const int *slots, float *vecs, uint8_t *u8, float *blob, int dump_layer,

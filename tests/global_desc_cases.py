@@ -50,6 +50,7 @@ def load_emu():
         L.emu_gd_job_floats.restype = C.c_longlong
         L.emu_gd_configure.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
         L.emu_gd_describe.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.emu_gd_pw_tiles.argtypes = [C.c_longlong, C.c_int, C.c_int]
         _emu = L
     return _emu
 
@@ -145,7 +146,133 @@ def case_prep(wh, **more):
     return p
 
 
-# ---- refusals of configure: name -> (layers, params transform, prep, words of the message) ----------------------------------------
+# ---- the batch cases: job counts at which the launcher takes k_gd_pw_mfma<4> and <2> (tests/test_gpu_global_desc_batch.py) ----------
+BATCH_WH = (7, 5)                            # 35 pixels per job: a pixel tile of 32 straddles two jobs
+BATCH_HW = BATCH_WH[0] * BATCH_WH[1]
+JOBS_NT4, JOBS_NT4_EXACT, JOBS_NT2 = 1873, 1872, 1871          # 2049, 2048 and 2047 pixel tiles
+
+
+def pw_tiles(hw, njobs, cout):
+    """the NT of k_gd_pw_mfma<NT> the launcher takes for a PW layer (csrc/k_global_desc.h, gd_pw_tiles)"""
+    return int(load_emu().emu_gd_pw_tiles(int(hw), int(njobs), (int(cout) + 31) & ~31))
+
+
+def batch_net(cin, cout, relu6=0):
+    """PW 3 -> cin, the PW cin -> cout under test, and a DW3 in front of the pool: its 9 taps make the result depend on where each
+    pixel of the PW's output landed, which the pool's sum alone often does not"""
+    return [(PW, 3, cin, 1, 0, -1), (PW, cin, cout, 1, relu6, -1), (DW3, cout, cout, 1, 0, -1), (AVGPOOL, cout, cout, 1, 0, -1)]
+
+
+def batch_residual_net():
+    return [(PW, 3, 40, 1, 0, -1), (PW, 40, 130, 1, 1, -1), (PW, 130, 40, 1, 0, 0), (DW3, 40, 40, 1, 0, -1), (AVGPOOL, 40, 40, 1, 0, -1)]
+
+
+def big_cout_net():
+    """the largest cout a table may hold, on a 1 x 1 prep: k_gd_conv3's grid.y is cout"""
+    return [(CONV3, 3, 1 << 16, 1, 0, -1), (PW, 1 << 16, 4, 1, 0, -1), (AVGPOOL, 4, 4, 1, 0, -1)], (1, 1)
+
+
+def batch_slots(n):
+    """neighbouring jobs read different images"""
+    return np.asarray((2, 0, 1), np.int32)[np.arange(n) % 3]
+
+
+def param_spans(layers):
+    """per layer (start of the weights, start of the bias, end) in the flat parameter array"""
+    out, o = [], 0
+    for l in layers:
+        nw = {CONV3: l[2] * l[1] * 9, DW3: l[2] * 9, PW: l[2] * l[1]}.get(l[0])
+        if nw is None:
+            out.append((o, o, o))
+            continue
+        out.append((o, o + nw, o + nw + l[2]))
+        o += nw + l[2]
+    return out
+
+
+def scale_bias(layers, prm, f):
+    prm = np.array(prm, np.float32)
+    for w0, b0, e in param_spans(layers):
+        prm[b0:e] *= np.float32(f)
+    return prm
+
+
+def zero_bias(layers, prm):
+    return scale_bias(layers, prm, 0.0)
+
+
+def scale_weights(layers, prm, li, f):
+    prm = np.array(prm, np.float32)
+    w0, b0, e = param_spans(layers)[li]
+    prm[w0:b0] *= np.float32(f)
+    return prm
+
+
+SUBNORMAL_REGIMES = ("activations", "weights", "edge")
+
+
+def subnormal_case(regime, seed=11):
+    """(layers, params, prep, classes the host result has to hold): f32 subnormals as the MFMA's B input and accumulator (activations:
+    the blob is (pix - mean) 2^-134), as its A input (weights: the first layer's times 2^-130), and accumulators that cross the edge of
+    the normal range (edge: blob times 2^-128 against biases times 2^-118)"""
+    layers = batch_net(33, 65)
+    prm = seeded(layers, seed)
+    if regime == "activations":
+        return layers, zero_bias(layers, prm), case_prep(BATCH_WH, scale=2.0 ** -134), ("subnormal",)
+    if regime == "weights":
+        return layers, scale_weights(layers, zero_bias(layers, prm), 0, 2.0 ** -130), case_prep(BATCH_WH), ("subnormal",)
+    assert regime == "edge"
+    return layers, scale_bias(layers, prm, 2.0 ** -118), case_prep(BATCH_WH, scale=2.0 ** -128), ("subnormal", "normal")
+
+
+def overflow_case(relu6, imgs, seed=13):
+    """(layers, params, prep): infinities enter the PW 33 -> 65 under test and NaN arises inside its chain.  A chain of fmaf over finite
+    inputs never gives NaN (a product is exact, so inf - inf needs an infinite input), hence the infinities are made one layer earlier,
+    by the first PW: with mean 0 and scale = (FLT_MAX / 3e38) / (t - 0.5) its weights (3e38, 0, 0) and (-3e38, 0, 0) make channel 0
+    +inf and channel 1 -inf at the pixels >= t and leave them finite elsewhere; t is one above the largest pixel of the darkest of
+    imgs (the resized u8 images by ref_global_desc, which equal the library's in every byte), so one image stays finite throughout.
+    Output channel co of the layer under test, by co % 8, at a pixel >= t: 0: weights (0.25, -0.25) on inputs 0 and 1, +inf; 1:
+    (-0.25, 0.25), -inf; 2: (0.25, 0.25), inf - inf = NaN; 3: (0, 0), 0 inf = NaN; 4 .. 7: seeded, whatever the signs give.  The DW3
+    behind it takes |w| on the channels 0 and 1, so that their infinities keep the sign up to the pool"""
+    import ref_global_desc as rg
+    top = sorted(int(rg.prep(im, BATCH_WH[0], BATCH_WH[1])[0].max()) for im in imgs)
+    t = top[0] + 1
+    assert 1 < t <= top[1], top
+    layers = batch_net(33, 65, relu6)
+    prm = seeded(layers, seed)
+    S = param_spans(layers)
+    big = np.float32(3.0e38)
+    w0 = prm[S[0][0]:S[0][1]].reshape(33, 3)
+    w0[0] = (big, 0, 0)
+    w0[1] = (-big, 0, 0)
+    prm[S[0][1]:S[0][1] + 2] = 0
+    w1 = prm[S[1][0]:S[1][1]].reshape(65, 33)
+    w2 = prm[S[2][0]:S[2][1]].reshape(65, 9)
+    pair = {0: (0.25, -0.25), 1: (-0.25, 0.25), 2: (0.25, 0.25), 3: (0.0, 0.0)}
+    for co in range(65):
+        if co % 8 in pair:
+            w1[co, :2] = pair[co % 8]
+        if co % 8 < 2:
+            w2[co] = np.abs(w2[co])
+    scale = float(np.finfo(np.float32).max) / 3.0e38 / (t - 0.5)
+    return layers, prm, case_prep(BATCH_WH, mean=(0.0, 0.0, 0.0), scale=scale)
+
+
+def float_classes(a):
+    """share of zeros, subnormals, normals, infinities and NaNs among the floats of a"""
+    m = bits(a).reshape(-1) & np.uint32(0x7FFFFFFF)
+    n = float(max(m.size, 1))
+    return dict(zero=(m == 0).sum() / n, subnormal=((m > 0) & (m < 0x00800000)).sum() / n,
+                normal=((m >= 0x00800000) & (m < 0x7F800000)).sum() / n, inf=(m == 0x7F800000).sum() / n, nan=(m > 0x7F800000).sum() / n)
+
+
+def chunks_of(njobs):
+    """the sizes of the chunks the configured network (host build) splits a call of njobs into"""
+    c = int(load_emu().emu_gd_chunk(int(njobs)))
+    return [min(c, njobs - j0) for j0 in range(0, njobs, c)]
+
+
+# ---- refusals of configure: name ->(layers, params transform, prep, words of the message) ----------------------------------------
 def refusals():
     """[(name, kwargs of a refused configure, words, kwargs of the accepted neighbour)]; kwargs: layers, prep, mutate (on params), nparams"""
     good = tiny_net()[0]

@@ -1,7 +1,8 @@
 """csrc/k_global_desc.h itself, compiled for the host (tests/cpp/gd_host_emu, -ffp-contract=off, std::fmaf), without a device:
 prep against tests/ref_global_desc.py in every byte and every f32; single layers against float64 inside the standard bound of a chain of
 n roundings, gamma_n (|bias| + sum |w x|), computed per output element; MobileNetV2 on seeded weights against float64 within four times
-the error a torch f32 evaluation of the same network shows; the chunking; every refusal with its accepted neighbour.
+the error a torch f32 evaluation of the same network shows; the chunking; every refusal with its accepted neighbour; the nets that
+work in the subnormal range, with the bound's underflow term; the launcher's choice of k_gd_pw_mfma<NT> (gd_pw_tiles) at its edges.
 Not a replacement for tests/test_gpu_global_desc.py: the compiler, the ISA, the MFMA and the launches are not in it."""
 import ctypes as C
 
@@ -51,13 +52,15 @@ def test_prep_takes_mean_and_scale():
     assert np.array_equal(gc.bits(r["blob"][0]), gc.bits(blob)) and np.abs(blob).max() < 3
 
 
-def _layer_check(layers, li, out_wh, src=(97, 53), seed=7):
-    """layer li of the net, host build against float64 on the host build's own input of that layer; per-element bound"""
-    prm = gc.seeded(layers, seed)
-    assert gc.emu_configure(src[0], src[1], layers, prm, gc.case_prep(out_wh))[0] == 0
+def _layer_check(layers, li, out_wh, src=(97, 53), seed=7, prm=None, prep=None, underflow=False):
+    """layer li of the net, host build against float64 on the host build's own input of that layer; per-element bound.  underflow:
+    the chain may round in the subnormal range, where a rounding costs up to half of 2^-149 whatever the magnitude: + n 2^-149"""
+    prm = gc.seeded(layers, seed) if prm is None else prm
+    prep = dict(gc.PREP_DEFAULTS, **(gc.case_prep(out_wh) if prep is None else prep))
+    assert gc.emu_configure(src[0], src[1], layers, prm, prep)[0] == 0
     imgs = gc.images(*src)
     slots = [0, 1, 2]
-    x64, outs = rg.forward(layers, prm, np.stack([rg.prep(imgs[s], *out_wh)[1] for s in slots]))
+    x64, outs = rg.forward(layers, prm, np.stack([rg.prep(imgs[s], out_wh[0], out_wh[1], prep["mean"], prep["scale"])[1] for s in slots]))
     shp = lambda i: tuple(outs[i].shape[1:]) if i >= 0 else (3, out_wh[1], out_wh[0])
 
     def dumped(i):
@@ -77,7 +80,7 @@ def _layer_check(layers, li, out_wh, src=(97, 53), seed=7):
     n = rg.chain_length(l, x.shape[2] * x.shape[3])
     if l[0] == rg.AVGPOOL:
         mag = mag / float(x.shape[2] * x.shape[3])
-    bound = rg.gamma(n) * mag
+    bound = rg.gamma(n) * mag + (n * 2.0 ** -149 if underflow else 0.0)
     err = np.abs(got.astype(np.float64) - want)
     worst = float((err / np.maximum(bound, 1e-300)).max())
     print("layer %d %s n = %d: worst error / bound = %.3f, max error %.3g" % (li, l, n, worst, err.max()))
@@ -114,6 +117,54 @@ def test_relu6_clamps_both_ways_and_pins_zero():
     assert gc.emu_configure(16, 16, layers, np.concatenate([w.reshape(-1), b]), gc.case_prep((2, 2)))[0] == 0
     v = gc.emu_describe(gc.images(16, 16), [0])["vecs"][0]
     assert gc.bits(v).tolist() == gc.bits(np.array([0.0, 6.0, 2.5, 0.0], np.float32)).tolist()
+
+
+@pytest.mark.parametrize("regime", gc.SUBNORMAL_REGIMES)
+def test_subnormal_regimes_against_float64(regime):
+    """the nets the device test runs bit for bit against this build (test_gpu_global_desc_batch.py), here against float64: every layer
+    inside gamma_n S + n 2^-149.  The classes are a condition: the case is about subnormals only while the host build produces them"""
+    layers, prm, prep, classes = gc.subnormal_case(regime)
+    for li in range(len(layers)):
+        got, want = _layer_check(layers, li, gc.BATCH_WH, prm=prm, prep=prep, underflow=True)
+    share = gc.float_classes(got)
+    print(regime, "descriptor:", {k: round(float(v), 3) for k, v in share.items()})
+    assert share["zero"] == 0 and share["nan"] == 0 and share["inf"] == 0 and all(share[c] >= 0.01 for c in classes), share
+    assert (want != 0).all()
+
+
+# ---- which k_gd_pw_mfma<NT> the launcher takes (gd_pw_tiles) ----------------------------------------------------------------------
+PW_TILE_EDGES = {       # jobs -> NT for cout = 31, 33, 65, 128, 129, 160, 256 on a 7 x 5 map: 2047, 2048, 2049 and 4 pixel tiles
+    1871: (1, 1, 2, 2, 4, 4, 4),
+    1872: (4, 4, 4, 4, 4, 4, 4),
+    1873: (4, 4, 4, 4, 4, 4, 4),
+    3: (1, 1, 1, 1, 1, 1, 1),
+}
+PW_TILE_MOBILENET = {1: (0, 0, 34), 3: (0, 1, 33), 39: (6, 6, 22), 64: (9, 7, 18)}      # jobs -> PW layers on <4>, <2>, <1> at 224 x 224
+
+
+def test_pw_tile_rule_at_its_edges():
+    assert gc.BATCH_HW == 35
+    for jobs, want in PW_TILE_EDGES.items():
+        got = tuple(gc.pw_tiles(35, jobs, cout) for cout in (31, 33, 65, 128, 129, 160, 256))
+        assert got == want, (jobs, got)
+    assert gc.pw_tiles(1, 1, 1) == 1 and gc.pw_tiles(1, 1, 1 << 16) == 1            # one pixel tile times 2048 channel tiles: 2048 waves at <1> only
+    assert gc.pw_tiles(224 * 224, 8192, 1280) == 4                                   # 12.8 M pixel tiles: the count is 64-bit
+
+
+def test_pw_tile_rule_on_the_mobilenet_table():
+    T = gd.mobilenet_v2_layers()
+    h = w = 224
+    pw = []
+    for op, cin, cout, stride, relu6, add_from in T:
+        if op in (gc.CONV3, gc.DW3):
+            h, w = (h + 2 - 3) // stride + 1, (w + 2 - 3) // stride + 1
+        if op == gc.PW:
+            pw.append((h * w, cout))
+    assert len(pw) == 34 and pw[0] == (112 * 112, 16) and pw[-1] == (7 * 7, 1280)
+    for jobs, want in PW_TILE_MOBILENET.items():
+        nt = [gc.pw_tiles(hw, jobs, cout) for hw, cout in pw]
+        assert tuple(nt.count(k) for k in (4, 2, 1)) == want, (jobs, nt)
+    assert gc.pw_tiles(112 * 112, 3, 96) == 2                                        # the one layer on <2> with three jobs: 16 -> 96
 
 
 def test_whole_network_within_four_times_torch_f32_s_own_error():
