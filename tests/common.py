@@ -33,14 +33,14 @@ def pkg():
 LL_CTX_KW = dict(max_slots=1, max_jobs=16, max_kf=11, max_lm=4096, max_obs=16384)
 
 
-def make_ll_ctx(svs, shards, resident):
+def make_ll_ctx(svs, shards, resident, max_kf=None):
     """a low-latency context with `shards` workgroups per problem and the LM trace on.  resident = 1: problems whose shards all
-    fit LDS go to k_ba_ll, the others to k_local_ba_t<2>; 0: all to the latter"""
+    fit LDS go to k_ba_ll, the others to k_local_ba_t<2>; 0: all to the latter.  max_kf: another window than LL_CTX_KW's 11"""
     old = {k: os.environ.get(k) for k in ("SVSLAM_LL_SHARDS", "SVSLAM_LL_RESIDENT")}
     os.environ["SVSLAM_LL_SHARDS"] = str(shards)
     os.environ["SVSLAM_LL_RESIDENT"] = str(resident)
     try:
-        c = svs.Context(W, H, **LL_CTX_KW)
+        c = svs.Context(W, H, **(LL_CTX_KW if max_kf is None else dict(LL_CTX_KW, max_kf=max_kf)))
         c.low_latency(True)
     finally:
         for k, v in old.items():
@@ -201,6 +201,28 @@ def ba_job(p, keep=None, sort=False):
         o = np.lexsort((okf, olm))
         okf, olm, ori, ouv = okf[o], olm[o], ori[o], ouv[o]
     return p["poses0"], p["pts0"], okf, olm, ori, ouv
+
+
+def against_oracle(got, ref, what, worst=None, skip_lm=None, skip_edge=None):
+    """a local-BA result (poses, points, chi2, iterations) against the oracle's at the project's tolerances (those of
+    test_gpu_parity.py and test_gpu_general_rig.py): iterations equal, translation 1e-6 m, quaternion 1e-7, points rtol / atol
+    1e-6, chi2 rtol 1e-5 atol 1e-6.  The deviations are printed before they are asserted and their maxima kept in `worst`."""
+    (poses, pts, chi2, it), (pr, xr, cr, itr) = got, ref[:4]
+    lm = np.ones(len(pts), bool) if skip_lm is None else ~skip_lm
+    ed = np.ones(len(chi2), bool) if skip_edge is None else ~skip_edge
+    dev = dict(t=np.abs(poses[:, 4:] - pr[:, 4:]).max(), q=np.abs(poses[:, :4] - pr[:, :4]).max(),
+               points=(np.abs(pts - xr) / (1 + np.abs(xr)))[lm].max(), chi2=(np.abs(chi2 - cr) / (0.1 + np.abs(cr)))[ed].max())
+    print("%-66s vs oracle: t %.1e m, q %.1e, points %.1e (rel), chi2 %.1e (rel), %d iterations"
+          % (what, dev["t"], dev["q"], dev["points"], dev["chi2"], it))
+    if worst is not None:
+        for k, v in dev.items():
+            worst[k] = max(worst[k], float(v))
+    assert it == itr, (what, it, itr)
+    assert np.allclose(poses[:, 4:], pr[:, 4:], atol=1e-6), (what, dev)
+    assert np.allclose(poses[:, :4], pr[:, :4], atol=1e-7), (what, dev)
+    assert np.allclose(pts[lm], xr[lm], rtol=1e-6, atol=1e-6), (what, dev)
+    assert np.allclose(chi2[ed], cr[ed], rtol=1e-5, atol=1e-6), (what, dev)
+    return dev
 
 
 def reproj_chi2(rig, poses, pts, okf, olm, ori, ouv):

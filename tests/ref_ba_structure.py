@@ -23,6 +23,10 @@ The constants below restate csrc/k_ba.h and csrc/k_ba_build.h.  Whoever changes 
   BB_THREADS, bb_lds_ints, bb_edge_cache_fits, bb_lds_bytes                                    k_ba_build.h:19, 54-64
   LL_ECAP, LL_LCAP, ba_lds_fixed_bytes_ll, ba_tile_cap_ll                                      k_ba.h (low-latency shards)
   LlCaps, ba_ll_lds_bytes, ba_ll_caps                                                          k_ba_ll.h:23-46
+  the dealing rule (ll_deal)                                                                   k_ba_build.h:327-332, 386-396
+  what k_ba_build does for a shard (structure(no_group, all_active))                           k_ba_build.h:150-151, 172-173
+  ll_shard_in_lds                                                                              k_ba.h "const bool ll_res"
+  ll_enabled, ll_tile_cap                                         svslam_hip.hip svslam_set_low_latency, ba_ll_tile_cap
 """
 import numpy as np
 
@@ -78,9 +82,9 @@ def bb_lds_bytes(max_nlm, max_nobs=0):
 
 
 # ---- the low-latency solver: a problem dealt to shards, each solved by a kernel that keeps the shard in LDS when it fits
-# Unlike structure() below, which is written from the rule and held to brute force, these three are the LDS budgets of k_ba.h /
-# k_ba_ll.h and the fit test of k_ba_split restated term by term: a test that uses them checks the bookkeeping (the solver code
-# follows from the shard sizes the library reports), it is no second opinion on the formulas.
+# The capacities are the LDS budgets of k_ba.h / k_ba_ll.h and the fit test of k_ba_split restated term by term
+# (tests/test_ref_ba_structure.py pins their values at max_kf 7, 11, 13, 16, 17); the shard sizes they are applied to come from
+# ll_deal below, which is written from the dealing rule and held to a loop-only second implementation.
 LL_ECAP = 704
 LL_LCAP = 448
 BAREC_BYTES = 16            # BaRec: two floats, two ints
@@ -127,16 +131,88 @@ def ll_shards_fit(max_kf, shard_nlm, shard_nobs, shard_nblk):
                 and np.all(np.asarray(shard_nobs) <= E))
 
 
-def structure(nkf, nlm, okf, olm, cap):
+def ll_enabled(max_kf):
+    """svslam_set_low_latency makes the shard solver only where the streaming kernel's tile holds a landmark seen from every
+    keyframe and at least 64 blocks: tile_cap_ll(max_kf) >= max(max_kf, 64) (true up to max_kf 16)"""
+    return tile_cap_ll(max_kf) >= max(max_kf, 64)
+
+
+def ll_tile_cap(max_kf, resident):
+    """ba_ll_tile_cap: the tile capacity the shards are built with is what BOTH shard kernels hold, min(tile_cap_ll, B) in a
+    context with the resident kernel, tile_cap_ll in one without (SVSLAM_LL_RESIDENT=0: B = 0)"""
+    t, B = tile_cap_ll(max_kf), ll_caps(max_kf)[0]
+    return min(t, B) if resident and B > 0 else t
+
+
+def ll_shard_in_lds(nlm, nobs):
+    """k_local_ba_t<2>: a shard's records and positions live in LDS when it has at most LL_ECAP edges and LL_LCAP landmarks,
+    decided per shard"""
+    return nobs <= LL_ECAP and nlm <= LL_LCAP
+
+
+def ll_deal(olm, okf, nlm, W):
+    """k_ba_split's dealing rule for the edges (olm[e], okf[e]), landmark-major with keyframes ascending inside a landmark,
+    over W shards.  A landmark with e edges costs e (4 + e); the shard of a landmark is floor(cost of the landmarks before it
+    x W / total cost), at most W - 1; the shards are contiguous ranges in landmark order and a shard nothing fell into is the
+    empty range at the next shard's first landmark (at nlm behind the last); the mask has a bit for every shard with an edge;
+    a block is a distinct (landmark, keyframe) pair.  Python integers throughout.
+    Returns dict(cut [W + 1], nlm [W], nobs [W], nblk [W], mask)."""
+    olm = [int(v) for v in olm]; okf = [int(v) for v in okf]
+    assert len(olm) == len(okf) >= 1 and all(0 <= l < nlm for l in olm)
+    assert all((olm[i], okf[i]) <= (olm[i + 1], okf[i + 1]) for i in range(len(olm) - 1)), "edges are not landmark-major"
+    edges = [0] * nlm
+    for l in olm:
+        edges[l] += 1
+    cost = [e * (4 + e) for e in edges]
+    before = [sum(cost[:l]) for l in range(nlm)]
+    total = sum(cost)
+    shard = [min(before[l] * W // total, W - 1) for l in range(nlm)]
+    assert all(shard[l] <= shard[l + 1] for l in range(nlm - 1))
+    cut = [None] * W + [nlm]
+    for w in range(W - 1, -1, -1):
+        own = [l for l in range(nlm) if shard[l] == w]
+        cut[w] = own[0] if own else cut[w + 1]
+    blocks = sorted(set(zip(olm, okf)))
+    s_nlm = [cut[w + 1] - cut[w] for w in range(W)]
+    s_nobs = [sum(edges[cut[w]:cut[w + 1]]) for w in range(W)]
+    s_nblk = [sum(1 for l, _ in blocks if cut[w] <= l < cut[w + 1]) for w in range(W)]
+    mask = sum(1 << w for w in range(W) if s_nobs[w] > 0)
+    return dict(cut=cut, nlm=s_nlm, nobs=s_nobs, nblk=s_nblk, mask=mask)
+
+
+def ll_shards(olm, okf, nkf, nlm, W, max_kf, resident):
+    """what Context.ll_shards reports for the problem, one row per shard: landmarks, edges, blocks, tiles, solver code (2:
+    resident k_ba_ll, 1: streaming k_local_ba_t<2>), active poses, shard mask — the deal, k_ba_build's structure of every shard
+    (no_group, all_active; a shard without edges is not built: no blocks, tiles or poses), and k_ba_split's fit test.
+    Also returns the per-shard structures (None for a shard without edges)."""
+    olm = np.asarray(olm, np.int64); okf = np.asarray(okf, np.int64)
+    d = ll_deal(olm, okf, nlm, W)
+    cap = ll_tile_cap(max_kf, resident)
+    fits = bool(resident) and ll_shards_fit(max_kf, d["nlm"], d["nobs"], d["nblk"])
+    rows, structs = [], []
+    for w in range(W):
+        a, b = d["cut"][w], d["cut"][w + 1]
+        sel = (olm >= a) & (olm < b)
+        s = structure(nkf, b - a, okf[sel], olm[sel] - a, cap, no_group=True, all_active=True) if sel.any() else None
+        assert s is None or (s["nblk"] == d["nblk"][w] and s["nlm"] == d["nlm"][w])
+        structs.append(s)
+        rows.append([d["nlm"][w], d["nobs"][w], d["nblk"][w], s["ntile"] if s else 0, 2 if fits else 1, s["na"] if s else 0,
+                     d["mask"]])
+    return np.array(rows, np.int64), structs, d
+
+
+def structure(nkf, nlm, okf, olm, cap, no_group=False, all_active=False):
     """the structure of the problem with edges (okf[e], olm[e]), any order, for tiles of capacity `cap`; nobs >= 1
-    (a problem without edges is not built at all)"""
+    (a problem without edges is not built at all).  no_group, all_active: what k_ba_build is told for a low-latency shard —
+    ungrouped numbering whatever the key count (nmv = nlm: every landmark goes through the tiles, the ones without edges
+    too), and every keyframe an active pose (na = nkf)"""
     okf = np.asarray(okf, np.int64); olm = np.asarray(olm, np.int64)
     assert len(okf) == len(olm) >= 1 and okf.min() >= 0 and okf.max() < nkf and olm.min() >= 0 and olm.max() < nlm
     seen = np.zeros((nlm, nkf), bool)
     seen[olm, okf] = True
     blocks = seen.sum(1)                                         # per landmark, caller numbering
     maxc = int(blocks.max())
-    grouped = maxc >= 1 and maxc + nkf <= BB_MAXKEYS
+    grouped = not no_group and maxc >= 1 and maxc + nkf <= BB_MAXKEYS
     only_kf = seen.argmax(1)                                     # meaningful where blocks == 1
 
     def rank(l):
@@ -168,7 +244,7 @@ def structure(nkf, nlm, okf, olm, cap):
     items_lm = b * (b + 1) // 2
     tile_items = np.array([int(items_lm[tile_lm[t]:tile_lm[t + 1]].sum()) for t in range(ntile)], np.int64)
     tile_blocks = np.array([int(b[tile_lm[t]:tile_lm[t + 1]].sum()) for t in range(ntile)], np.int64)
-    na = int(seen.any(0).sum())
+    na = nkf if all_active else int(seen.any(0).sum())
     return dict(nkf=nkf, nlm=nlm, cap=cap, blocks=blocks, maxc=maxc, grouped=grouped, lm_orig=lm_orig, blocks_new=b, nmv=nmv,
                 sv_start=sv_start, na=na, nblk=int(blocks.sum()), tile_lm=tile_lm, ntile=ntile, tile_items=tile_items,
                 tile_blocks=tile_blocks, ncontrib=int(tile_items.sum()), npairs=na * (na + 1) // 2,

@@ -95,21 +95,8 @@ def _bit_equal(a, b, what):
 
 
 def _against_oracle(got, ref, what, skip_lm=None, skip_edge=None):
-    """(iii), printed before it is asserted"""
-    (poses, pts, chi2, it), (pr, xr, cr, itr) = got, ref[:4]
-    lm = np.ones(len(pts), bool) if skip_lm is None else ~skip_lm
-    ed = np.ones(len(chi2), bool) if skip_edge is None else ~skip_edge
-    dev = dict(t=np.abs(poses[:, 4:] - pr[:, 4:]).max(), q=np.abs(poses[:, :4] - pr[:, :4]).max(),
-               points=(np.abs(pts - xr) / (1 + np.abs(xr)))[lm].max(), chi2=(np.abs(chi2 - cr) / (0.1 + np.abs(cr)))[ed].max())
-    print("%-66s vs oracle: t %.1e m, q %.1e, points %.1e (rel), chi2 %.1e (rel), %d iterations"
-          % (what, dev["t"], dev["q"], dev["points"], dev["chi2"], it))
-    for k, v in dev.items():
-        WORST[k] = max(WORST[k], float(v))
-    assert it == itr, (what, it, itr)
-    assert np.allclose(poses[:, 4:], pr[:, 4:], atol=1e-6), (what, dev)
-    assert np.allclose(poses[:, :4], pr[:, :4], atol=1e-7), (what, dev)
-    assert np.allclose(pts[lm], xr[lm], rtol=1e-6, atol=1e-6), (what, dev)
-    assert np.allclose(chi2[ed], cr[ed], rtol=1e-5, atol=1e-6), (what, dev)
+    """(iii), printed before it is asserted (common.against_oracle)"""
+    cm.against_oracle(got, ref, what, WORST, skip_lm, skip_edge)
 
 
 def test_tile_capacities(svs):
@@ -168,13 +155,12 @@ def ll_ctx(svs, request):
 
 @pytest.mark.parametrize("case", LL_CASES, ids=repr)
 def test_structure_case_low_latency(ll_ctx, orc, case):
-    """submit / collect with the problem dealt to 4 and to 16 shards: which kernel solved it follows from the shard sizes
-    Context.ll_shards reports and the resident capacities (2 resident k_ba_ll, 1 streaming k_local_ba_t<2>), a shard
-    without edges is missing from the shard mask, results and LM trajectory are the oracle's.
-    ref_ba_structure.ll_shards_fit restates the capacity formulas of k_ba_ll.h and the fit test of k_ba_split term by term: that
-    assertion is bookkeeping (the code follows from the reported sizes), not an independent derivation.  The independent part is
-    LL_STREAMING: both kernels must be met, each by the cases named there.  The shards are tiled with at most 256 blocks here and
-    the dealing rule is not restated, so no case sits on the shard solvers' own tile boundary."""
+    """submit / collect with the problem dealt to 4 and to 16 shards: what Context.ll_shards reports — landmarks, edges, blocks,
+    tiles, solver (2 resident k_ba_ll, 1 streaming k_local_ba_t<2>), active poses and shard mask of every shard — equals the
+    restatement of the dealing rule, of k_ba_build's shard structure and of k_ba_split's fit test (ref_ba_structure.ll_shards;
+    ll_deal is held to a loop-only second implementation in test_ref_ba_structure.py), a shard without edges is missing from the
+    shard mask, results and LM trajectory are the oracle's.  LL_STREAMING names the cases that must meet the streaming kernel.
+    The shard solvers' own boundaries are in tests/test_gpu_ll_structure.py."""
     by_name = {c.name: k for k, c in enumerate(CASES)}
     p = cm.make_ba_problem_vis(np.random.default_rng(1 + by_name.get(case.name, len(CASES))), case.vis_l, case.vis_r)
     job = cm.ba_job(p, sort=True)
@@ -186,8 +172,8 @@ def test_structure_case_low_latency(ll_ctx, orc, case):
     tr = ll_ctx.lm_trace(job=0)
     assert sh.shape[0] == ll_ctx.shards
     assert sh[:, 0].sum() == case.nlm and sh[:, 1].sum() == len(job[2]) and sh[:, 2].sum() == case.structure()["nblk"]
-    fits = R.ll_shards_fit(LL_MAX_KF, sh[:, 0], sh[:, 1], sh[:, 2])
-    assert np.all(sh[:, 4] == (2 if fits else 1)), (case.name, "solver", sh[:, 4].tolist(), "shards fit" if fits else "a shard does not fit", sh[:, :3].tolist())
+    want, _, deal = R.ll_shards(job[3], job[2], case.nkf, case.nlm, ll_ctx.shards, LL_MAX_KF, 1)
+    assert np.array_equal(sh[:, :7], want), (case.name, "shards (landmarks, edges, blocks, tiles, solver, poses, mask)", sh[:, :7].tolist(), want.tolist(), deal["cut"])
     assert int(sh[0, 4]) == (1 if (ll_ctx.shards, case.name) in LL_STREAMING else 2), (case.name, ll_ctx.shards, "solver", int(sh[0, 4]), sh[:, :3].tolist())
     mask = int(sh[0, 6])
     assert np.all(sh[:, 6] == mask) and [(mask >> w) & 1 for w in range(ll_ctx.shards)] == (sh[:, 1] > 0).astype(int).tolist()

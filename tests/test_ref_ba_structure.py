@@ -129,6 +129,141 @@ def test_edge_cache_problem_and_partners():
     assert R.bb_lds_bytes(big) <= R.CREATE_BUILD_LDS_LIMIT and big < 65536
 
 
+# --------------------------------------------------------------------------- the low-latency solver: the deal, the capacities, the cases
+LL_BOUNDARY = bc.ll_boundary_cases()
+
+
+def _deal_one_landmark_at_a_time(olm, okf, nlm, W):
+    """the dealing rule again, without prefix arrays: walk the landmarks once with a running cost, open shards as the walk
+    reaches them"""
+    total = 0
+    for l in range(nlm):
+        e = sum(1 for v in olm if v == l)
+        total += e * (4 + e)
+    cut, nl, no, nb = [0], [0] * W, [0] * W, [0] * W
+    run = 0
+    for l in range(nlm):
+        kfs = [k for v, k in zip(olm, okf) if v == l]
+        w = run * W // total
+        if w > W - 1:
+            w = W - 1
+        while len(cut) - 1 < w:                  # the walk has passed into shard w: it, and every shard skipped, starts here
+            cut.append(l)
+        nl[w] += 1; no[w] += len(kfs); nb[w] += len(set(kfs))
+        run += len(kfs) * (4 + len(kfs))
+    while len(cut) < W + 1:
+        cut.append(nlm)
+    mask = 0
+    for w in range(W):
+        if no[w]:
+            mask |= 1 << w
+    return dict(cut=cut, nlm=nl, nobs=no, nblk=nb, mask=mask)
+
+
+def test_ll_deal_against_the_loop_only_implementation():
+    rng = np.random.default_rng(11)
+    seen = dict(front=0, middle=0, end=0, hole=0, trailing_hole=0, edgeless_shard=0)
+    for it in range(210):
+        W = (4, 8, 16)[it % 3]
+        nkf = int(rng.integers(2, 12)); nlm = int(rng.integers(1, 90))
+        vis = rng.random((nkf, nlm)) < float(rng.choice([0.1, 0.4, 0.9]))
+        if it % 5 == 0:
+            vis[:, rng.integers(nlm)] = True                                   # a landmark that outweighs several shares
+        bare = np.zeros(nlm, bool)
+        if it % 2 == 0 and nlm >= 6:
+            which = ("front", "middle", "end")[(it // 2) % 3]
+            n = int(rng.integers(1, 4))
+            bare[{"front": slice(0, n), "middle": slice(nlm // 2, nlm // 2 + n), "end": slice(nlm - n, nlm)}[which]] = True
+        vis[:, bare] = False
+        if not vis.any():
+            vis[0, int(np.nonzero(~bare)[0][0])] = True
+        has = vis.any(0)
+        seen["front"] += not has[0]; seen["end"] += not has[-1]; seen["middle"] += bool((~has[1:-1]).any())
+        olm, okf = np.nonzero(vis.T)                                           # landmark-major, keyframes ascending
+        dup = rng.random(len(olm)) < 0.5                                       # the block's second edge
+        o = np.lexsort((np.concatenate([okf, okf[dup]]), np.concatenate([olm, olm[dup]])))
+        olm, okf = np.concatenate([olm, olm[dup]])[o], np.concatenate([okf, okf[dup]])[o]
+        d = R.ll_deal(olm, okf, nlm, W)
+        assert d == _deal_one_landmark_at_a_time(olm.tolist(), okf.tolist(), nlm, W), (it, W)
+        c = d["cut"]
+        assert c[0] == 0 and c[W] == nlm and all(c[w] <= c[w + 1] for w in range(W)), "the ranges partition [0, nlm) in order"
+        assert [c[w + 1] - c[w] for w in range(W)] == d["nlm"]
+        assert sum(d["nlm"]) == nlm and sum(d["nobs"]) == len(olm) and sum(d["nblk"]) == len(set(zip(olm.tolist(), okf.tolist())))
+        assert d["mask"] == sum(1 << w for w in range(W) if d["nobs"][w] > 0)
+        # nothing costs anything before the first landmark with edges, so it is dealt to shard 0: the leader (the lowest shard of
+        # the mask, which writes the poses and the trace back) is always shard 0
+        assert d["mask"] & 1, "shard 0 without edges"
+        holes = [w for w in range(W) if d["nlm"][w] == 0]
+        seen["hole"] += any(any(d["nobs"][v] for v in range(w + 1, W)) for w in holes)
+        seen["trailing_hole"] += any(not any(d["nlm"][v] for v in range(w, W)) for w in holes)
+        seen["edgeless_shard"] += any(d["nlm"][w] > 0 and d["nobs"][w] == 0 for w in range(W))
+    assert min(seen.values()) >= 10, seen
+
+
+def test_ll_capacity_table():
+    """tile_cap_ll / ll_caps as the cases of ba_structure_cases.ll_boundary_cases are written for them; the shard solver exists
+    up to max_kf 16; the two capacities of ba_ll_tile_cap differ on both sides"""
+    want = {7: (368, (320, 208, 448)), 11: (256, (256, 208, 448)), 13: (176, (192, 208, 448)), 16: (64, (64, 208, 448)),
+            17: (0, (0, 0, 0))}
+    for max_kf, (t, caps) in want.items():
+        assert (R.tile_cap_ll(max_kf), R.ll_caps(max_kf)) == (t, caps), (max_kf, R.tile_cap_ll(max_kf), R.ll_caps(max_kf))
+    assert [R.ll_enabled(k) for k in (1, 7, 11, 16, 17, 20)] == [True, True, True, True, False, False]
+    assert [R.ll_tile_cap(k, 1) for k in (7, 11, 13, 16)] == [320, 256, 176, 64]
+    assert [R.ll_tile_cap(k, 0) for k in (7, 11, 13, 16)] == [368, 256, 176, 64]
+    assert (R.LL_ECAP, R.LL_LCAP) == (704, 448)
+    assert R.ll_shard_in_lds(448, 704) and not R.ll_shard_in_lds(449, 704) and not R.ll_shard_in_lds(448, 705)
+    for max_kf in range(1, 33):
+        if not R.ll_enabled(max_kf):
+            continue
+        B, L, E = R.ll_caps(max_kf)
+        assert B >= 64 and R.ll_resident_lds_bytes(max_kf, B, L, E) <= R.BA_LDS_LIMIT
+        # k_ba_ll stages min(ncontrib, BA_PIT_CAP) pair items in LDS and would read the others from g_pitem; a resident shard has
+        # one tile of at most min(tile_cap_ll, B) blocks, a landmark of m <= max_kf blocks lists m (m + 1) / 2 items, so at most
+        # B (max_kf + 1) / 2 items: below BA_PIT_CAP everywhere, the fallback is unreachable
+        items = R.ll_tile_cap(max_kf, 1) * (max_kf + 1) // 2
+        assert items < R.BA_PIT_CAP, (max_kf, items)
+        if max_kf == 11:
+            assert items == 1536
+
+
+@pytest.mark.parametrize("case", LL_BOUNDARY, ids=repr)
+def test_ll_boundary_case(case):
+    okf, olm = case.edges()
+    assert np.array_equal(np.lexsort((okf, olm)), np.arange(len(olm))), "edges are not landmark-major"
+    assert R.ll_enabled(case.max_kf) and case.nkf <= case.max_kf and case.W in (4, 8, 16)
+    assert case.nlm <= cm.LL_CTX_KW["max_lm"] and len(olm) <= cm.LL_CTX_KW["max_obs"]
+    t, structs, d = case.shards()
+    assert d == _deal_one_landmark_at_a_time(olm.tolist(), okf.tolist(), case.nlm, case.W)
+    assert case.prop(t), (case.name, t.tolist())
+    # which kernel: all shards inside the three resident capacities and the tile, in a context that has the resident kernel
+    cap = R.ll_tile_cap(case.max_kf, case.resident)
+    B, L, E = R.ll_caps(case.max_kf)
+    fits = case.resident and t[:, 2].max() <= min(B, cap) and t[:, 0].max() <= min(L, cap) and t[:, 1].max() <= E
+    assert np.all(t[:, 4] == (2 if fits else 1))
+    for w, s in enumerate(structs):
+        if s is not None:
+            assert not s["grouped"] and s["nmv"] == s["nlm"] and s["na"] == case.nkf
+            assert t[w, 3] == s["ntile"] >= 1 and (t[w, 4] == 1 or s["ntile"] == 1)
+            assert s["ncontrib"] < R.BA_PIT_CAP or t[w, 4] == 1
+    # no landmark with a single edge: nothing is excluded from the comparison with the oracle
+    nedge = case.vis_l.sum(0) + case.vis_r.sum(0)
+    assert not (nedge == 1).any() and (nedge >= 2).any(0)
+    assert (case.vis_l | case.vis_r).any(1).all(), "a keyframe without edges"
+
+
+def test_ll_boundary_case_names():
+    names = [c.name for c in LL_BOUNDARY]
+    assert len(set(names)) == len(names)
+    for word in ("res-w4-blocks-256", "res-w4-blocks-257-in-shard-0", "257-in-a-middle-shard", "257-in-the-last-shard", "res-w8-blocks-25",
+                 "res-w16-blocks-25", "stream-w4-blocks-256", "stream-w4-blocks-257", "landmarks-208", "landmarks-209", "edges-448",
+                 "edges-449", "in-lds-edges-704", "in-lds-edges-705", "in-lds-landmarks-448", "in-lds-landmarks-449", "kf7-res-w4-blocks-320",
+                 "kf7-res-w4-blocks-321", "kf7-stream-w4-blocks-368", "kf7-stream-w4-blocks-369", "kf13-res-w4-blocks-176",
+                 "kf13-res-w4-blocks-177", "kf16-res-w4-blocks-64", "kf16-res-w4-blocks-65", "shard-mask-with-holes"):
+        assert any(word in n for n in names), word
+    for W in (4, 16):
+        assert sorted(c.nkf for c in LL_BOUNDARY if c.name.startswith("ll-kf16-res-w%d-" % W) and "keyframes" in c.name) == [2, 3, 5, 8, 12, 16]
+
+
 @pytest.mark.parametrize("name", ["cap64-tile0-exactly-full", "empty-right-camera-only-landmark", "rows-72"])
 def test_problem_builder_realises_the_masks(name):
     """make_ba_problem_vis asserts that itself; here: at 20 keyframes there is room in the intersection of the frusta, the
