@@ -691,6 +691,63 @@ int svslam_dmap_evicted(svslam_ctx *ctx, const svslam_dmap_evicted_rec **recs, i
 int svslam_dmap_read(svslam_ctx *ctx, int stream, long long *kf_frame, int *kf_id, double *kf_pose, int *kf_n,
                      int *lm_id, double *lm_pos, int *lm_obs, uint8_t *lm_state);
 
+/* ---- test hooks: the kernels of the device map one at a time, on maps the test chose (tests/test_gpu_dmap_kernels.py) ----
+ * Video drives the map only where natural runs go.  These hooks put one stream's map into any state and run ONE kernel of
+ * the keyframe path on it, launched by the very lines svslam_dmap_keyframe_batch launches it with.  Nothing here is meant
+ * for a caller that is not a test.
+ *
+ * One stream's whole map.  Per array: kf_* [max_kf], kf_pose [max_kf][7], f_* [max_kf][max_pts] (f_xy / f_xyr two floats per
+ * feature; f_lm / f_lmr the landmark SLOT the left / right feature observes, -1 none; f_fl bit 0: right feature found),
+ * lm_* [max_lm] (lm_pos [max_lm][3]; lm_stamp: last keyframe step whose tracked list named the landmark), next_lm_id [1].
+ * A null member is skipped.  The write refuses kf_n outside [0, max_pts] and slots outside [-1, max_lm): the kernels index
+ * with them.                                                                                                            */
+typedef struct svslam_dmap_state {
+    long long *kf_frame; int *kf_id; double *kf_pose; int *kf_n;
+    float *f_xy, *f_xyr; int *f_lm, *f_lmr; uint8_t *f_fl;
+    double *lm_pos; int *lm_id, *lm_obs; uint8_t *lm_state; int *lm_stamp, *next_lm_id;
+} svslam_dmap_state;
+int svslam_debug_dmap_write(svslam_ctx *ctx, int stream, const svslam_dmap_state *arrays);
+int svslam_debug_dmap_read(svslam_ctx *ctx, int stream, svslam_dmap_state *arrays);
+/* test hook: the resident feature list of `stream` as the next call would read it, max_pts entries each (null: skipped)  */
+int svslam_debug_rtrack_read(svslam_ctx *ctx, int stream, float *xy, int *mp, double *xyz);
+
+#define SVSLAM_DMAP_STAGE_BEGIN         0  /* k_dmap_begin:         in ev_quota; in/out evicted [njobs * ev_quota], ev_cursor [1]; the
+                                              resident lists (svslam_rtrack_upload) are the tracked survivors                       */
+#define SVSLAM_DMAP_STAGE_STEREO_PREP   1  /* k_dmap_stereo_prep:   in corners [njobs][max_corners][2], ncorners [njobs], cam_r;
+                                              out lkjobs [njobs], prev_xy / next_xy [njobs][max_pts][2]                            */
+#define SVSLAM_DMAP_STAGE_STEREO_FINISH 2  /* k_dmap_stereo_finish: in next_xy, status [njobs][max_pts], num_features_init, zmax;
+                                              out trijobs [njobs], uv_l / uv_r [njobs][max_pts][2], tri_idx [njobs][max_pts]      */
+#define SVSLAM_DMAP_STAGE_COMMIT        3  /* k_dmap_commit:        in tri_xyz [njobs][max_pts][3], tri_ok, tri_idx [njobs][max_pts];
+                                              the jobs' n_tri_in, dead                                                              */
+#define SVSLAM_DMAP_STAGE_BA_GATHER     4  /* k_dmap_ba_gather<threads>: in threads (512 | 1024), max_kf (<= 12), max_obs — the strides
+                                              of: out badev [njobs][SVSLAM_DMAP_BADEV_INTS], poses [njobs][max_kf][7], pts [njobs]
+                                              [max_lm][3], packed / edge_ref [njobs][max_obs], uv [njobs][max_obs][2], lm_slot_of
+                                              [njobs][max_lm]; the jobs' flags, ba_*, win_slot                                      */
+#define SVSLAM_DMAP_STAGE_BA_SCATTER    5  /* k_dmap_ba_scatter:    in badev (nkf, nlm, nobs, iters_done, ...), poses, pts, chi2
+                                              [njobs][max_obs], edge_ref, lm_slot_of, max_kf, max_obs, chi2_th; the jobs' win_slot  */
+#define SVSLAM_DMAP_STAGE_REFRESH       6  /* k_dmap_refresh:       the jobs' kf_slot, n_features; read back: svslam_debug_rtrack_read */
+#define SVSLAM_DMAP_STAGE_REFRESH_XYZ   7  /* k_dmap_refresh_xyz:   the jobs' stream, npts                                         */
+/* the gather's problem descriptor, one int each: kf_ofs, nkf, lm_ofs, nlm, obs_ofs, nobs, nblk, na, ncontrib, ntile, aux_ofs,
+ * iters_done, rec_ofs, lay_nblk, lay_na, lay_ntile, nmv, reserved, lm_base, shmask, ntrial                               */
+#define SVSLAM_DMAP_BADEV_INTS 21
+/* Every array a stage names is copied to the device before the launch and back after it, whole, so a test that fills an
+ * output with a pattern sees what the kernel did NOT write as well.  Arrays of other stages may be null.                  */
+typedef struct svslam_dmap_stage_io {
+    int    threads, max_kf, max_obs, ev_quota, max_corners, num_features_init;
+    double zmax, chi2_th, cam_r[4];
+    svslam_dmap_evicted_rec *evicted; int *ev_cursor;
+    const float *corners; const int *ncorners;
+    svslam_lk_job *lkjobs; float *prev_xy, *next_xy;
+    const uint8_t *status; svslam_tri_job *trijobs; float *uv_l, *uv_r; int *tri_idx;
+    const double *tri_xyz; const uint8_t *tri_ok;
+    int *badev; double *poses, *pts; unsigned int *packed; float *uv; int *edge_ref, *lm_slot_of;
+    const double *chi2;
+} svslam_dmap_stage_io;
+/* Runs stage `stage` for `njobs` jobs on distinct streams.  jobs goes to the device as the caller filled it (src_buf / dst_buf
+ * are set to the stream's current resident buffer, as the keyframe call sets them; the stamp is the caller's) and comes back
+ * as the kernel left it.  Indices a kernel would use unchecked (slots, counts, edge references) are validated first.       */
+int svslam_debug_dmap_stage(svslam_ctx *ctx, int stage, int njobs, svslam_dmap_job *jobs, const svslam_dmap_stage_io *io);
+
 /* host threads the library may use to prepare a batched call (per-problem BA structure
  * building); default 1.                                                        */
 int svslam_set_host_threads(svslam_ctx *ctx, int n);

@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "svslam_dev_alloc", "svslam_dev_free", "svslam_dev_upload", "svslam_dev_download", "svslam_sync",
     "svslam_timing_enable", "svslam_timing_reset", "svslam_timing_get", "svslam_ba_profile",
     "svslam_set_host_threads", "svslam_debug_host_ns", "svslam_debug_ll_shards", "svslam_debug_ll_limits", "svslam_debug_ba_struct", "svslam_debug_clock_mhz", "svslam_debug_hold_cus", "svslam_lm_trace",
+    "svslam_debug_dmap_write", "svslam_debug_dmap_read", "svslam_debug_rtrack_read", "svslam_debug_dmap_stage",
 ]
 
 FAMILIES = {"pyramid": 0, "lk": 1, "gftt": 2, "triangulate": 3, "pose_only": 4, "local_ba": 5}
@@ -188,6 +189,46 @@ class DenseJob(C.Structure):
 class TrackJob(C.Structure):
     _fields_ = [("prev_slot", C.c_int), ("next_slot", C.c_int), ("pt_ofs", C.c_int), ("npts", C.c_int),
                 ("pose", C.c_double * 7), ("n_tracked", C.c_int), ("n_inlier", C.c_int)]
+
+
+class DmapJob(C.Structure):
+    """svslam_dmap_job"""
+    _fields_ = [("stream", C.c_int), ("slot_cur", C.c_int), ("slot_right", C.c_int), ("is_init", C.c_int),
+                ("kf_slot", C.c_int), ("remove_slot", C.c_int), ("kf_id", C.c_int), ("npts", C.c_int), ("frame_id", C.c_longlong),
+                ("pose", C.c_double * 7), ("T_camr_w", C.c_double * 7), ("T_wc", C.c_double * 7), ("src_buf", C.c_int), ("dst_buf", C.c_int),
+                ("stamp", C.c_int), ("corners_dropped", C.c_int), ("ok", C.c_int), ("n_features", C.c_int), ("n_corners", C.c_int),
+                ("n_right_ok", C.c_int), ("n_tri_in", C.c_int), ("n_tri_ok", C.c_int), ("ba_nkf", C.c_int), ("ba_nlm", C.c_int),
+                ("ba_nobs", C.c_int), ("ba_iters", C.c_int), ("flags", C.c_int), ("dead", C.c_int), ("ba_npair", C.c_int),
+                ("ba_ntrial", C.c_int), ("ev_ofs", C.c_int), ("ev_n", C.c_int), ("win_pose", (C.c_double * 7) * 12),
+                ("win_slot", C.c_int * 12)]
+
+
+class DmapParams(C.Structure):
+    _fields_ = [("num_features", C.c_int), ("num_features_init", C.c_int), ("num_active_keyframes", C.c_int), ("ba_iters", C.c_int),
+                ("max_triangulation_depth", C.c_double), ("chi2_th", C.c_double), ("ba_defer", C.c_int), ("reserved", C.c_int)]
+
+
+# test hooks of the device map (svslam_debug_dmap_*): the arrays of one stream's map, (name, dtype, shape in terms of KW, NF, NL)
+DMAP_STATE_FIELDS = (("kf_frame", np.int64, "K"), ("kf_id", np.int32, "K"), ("kf_pose", np.float64, "K7"), ("kf_n", np.int32, "K"),
+                     ("f_xy", np.float32, "KF2"), ("f_xyr", np.float32, "KF2"), ("f_lm", np.int32, "KF"), ("f_lmr", np.int32, "KF"),
+                     ("f_fl", np.uint8, "KF"), ("lm_pos", np.float64, "L3"), ("lm_id", np.int32, "L"), ("lm_obs", np.int32, "L"),
+                     ("lm_state", np.uint8, "L"), ("lm_stamp", np.int32, "L"), ("next_lm_id", np.int32, "1"))
+DMAP_STAGES = {"begin": 0, "stereo_prep": 1, "stereo_finish": 2, "commit": 3, "ba_gather": 4, "ba_scatter": 5, "refresh": 6, "refresh_xyz": 7}
+DMAP_BADEV_INTS = 21
+DMAP_BADEV = ("kf_ofs", "nkf", "lm_ofs", "nlm", "obs_ofs", "nobs", "nblk", "na", "ncontrib", "ntile", "aux_ofs", "iters_done", "rec_ofs",
+              "lay_nblk", "lay_na", "lay_ntile", "nmv", "reserved", "lm_base", "shmask", "ntrial")
+
+
+class DmapState(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _, _ in DMAP_STATE_FIELDS]
+
+
+class DmapStageIO(C.Structure):
+    _fields_ = [("threads", C.c_int), ("max_kf", C.c_int), ("max_obs", C.c_int), ("ev_quota", C.c_int), ("max_corners", C.c_int),
+                ("num_features_init", C.c_int), ("zmax", C.c_double), ("chi2_th", C.c_double), ("cam_r", C.c_double * 4)] + \
+               [(name, C.c_void_p) for name in ("evicted", "ev_cursor", "corners", "ncorners", "lkjobs", "prev_xy", "next_xy", "status",
+                                                "trijobs", "uv_l", "uv_r", "tri_idx", "tri_xyz", "tri_ok", "badev", "poses", "pts",
+                                                "packed", "uv", "edge_ref", "lm_slot_of", "chi2")]
 
 
 _lib = None
@@ -865,6 +906,59 @@ class Context:
         self._chk(self.L.svslam_dmap_read(self.h, stream, _p(d["kf_frame"]), _p(d["kf_id"]), _p(d["kf_pose"]), _p(d["kf_n"]),
                                           _p(d["lm_id"]), _p(d["lm_pos"]), _p(d["lm_obs"]), _p(d["lm_state"])), "dmap_read")
         return d
+
+    def dmap_state_shapes(self):
+        KW, NF, NL = self.lim.max_kf, self.lim.max_pts, self.lim.max_lm
+        dims = {"K": (KW,), "K7": (KW, 7), "KF": (KW, NF), "KF2": (KW, NF, 2), "L": (NL,), "L3": (NL, 3), "1": (1,)}
+        return {name: (dt, dims[sh]) for name, dt, sh in DMAP_STATE_FIELDS}
+
+    def _dmap_state(self, arrays):
+        st = DmapState()
+        for name, (dt, shape) in self.dmap_state_shapes().items():
+            a = arrays[name]
+            if a.dtype != dt or a.shape != shape or not a.flags.c_contiguous:
+                raise ValueError("dmap state: %s must be a contiguous %s array of shape %s" % (name, np.dtype(dt).name, shape))
+            setattr(st, name, a.ctypes.data)
+        return st
+
+    def dmap_state_read(self, stream):
+        """test hook: every array of one stream's device-resident map (svslam_debug_dmap_read), a dict by the header's names"""
+        d = {name: np.zeros(shape, dt) for name, (dt, shape) in self.dmap_state_shapes().items()}
+        self._chk(self.L.svslam_debug_dmap_read(self.h, stream, C.byref(self._dmap_state(d))), "debug_dmap_read")
+        return d
+
+    def dmap_state_write(self, stream, arrays):
+        """test hook: seeds one stream's device-resident map (svslam_debug_dmap_write) from a dict as dmap_state_read returns it"""
+        self._chk(self.L.svslam_debug_dmap_write(self.h, stream, C.byref(self._dmap_state(arrays))), "debug_dmap_write")
+
+    def rtrack_read(self, stream):
+        """test hook: the resident feature list of a stream, max_pts entries (svslam_debug_rtrack_read)"""
+        n = self.lim.max_pts
+        xy = np.zeros((n, 2), np.float32); mp = np.zeros(n, np.int32); xyz = np.zeros((n, 3))
+        self._chk(self.L.svslam_debug_rtrack_read(self.h, stream, _p(xy), _p(mp), _p(xyz)), "debug_rtrack_read")
+        return xy, mp, xyz
+
+    def dmap_stage(self, stage, jobs, arrays=None, **scalars):
+        """test hook: one kernel of the keyframe path alone (svslam_debug_dmap_stage).  jobs: a ctypes array of DmapJob, updated in
+        place; arrays: {member of svslam_dmap_stage_io: contiguous numpy array of the header's size}, updated in place; scalars: its
+        int / double members (cam_r: four doubles)."""
+        io = DmapStageIO()
+        for k, v in scalars.items():
+            if k == "cam_r":
+                io.cam_r = (C.c_double * 4)(*[float(x) for x in v])
+            else:
+                setattr(io, k, v)
+        n, NF, NL = len(jobs), self.lim.max_pts, self.lim.max_lm
+        P, E, MK = n * NF, n * max(io.max_obs, 1), io.max_kf
+        nbytes = dict(evicted=16 * n * io.ev_quota, ev_cursor=4, corners=8 * n * io.max_corners, ncorners=4 * n, lkjobs=16 * n, prev_xy=8 * P,
+                      next_xy=8 * P, status=P, trijobs=C.sizeof(TriJob) * n, uv_l=8 * P, uv_r=8 * P, tri_idx=4 * P, tri_xyz=24 * P, tri_ok=P,
+                      badev=4 * DMAP_BADEV_INTS * n, poses=56 * n * MK, pts=24 * n * NL, packed=4 * E, uv=8 * E, edge_ref=4 * E,
+                      lm_slot_of=4 * n * NL, chi2=8 * E)
+        for k, a in (arrays or {}).items():
+            if not a.flags.c_contiguous or a.nbytes != nbytes[k]:
+                raise ValueError("dmap_stage: %s must be contiguous and hold %d bytes, not %d" % (k, nbytes[k], a.nbytes))
+            setattr(io, k, a.ctypes.data)
+        self._chk(self.L.svslam_debug_dmap_stage(self.h, DMAP_STAGES[stage], len(jobs), jobs, C.byref(io)), "debug_dmap_stage(%s)" % stage)
 
     # ---- resident tracking -----------------------------------------------------
     def rtrack_upload(self, lists):
