@@ -1,0 +1,330 @@
+// api_dense.h — included by svslam_hip.hip.  Entry points: svslam_stereo_bm_*, svslam_dense_cloud_batch, svslam_cloud_sor_batch,
+// svslam_cloud_voxel_grid, svslam_debug_cloud_sor_climbs.  Owns of svslam_ctx: bm, cf.
+
+extern "C" {
+
+// ------------------------------------------------------------------ dense stereo (run_dense_reconstruction)
+static int bm_check_params(svslam_ctx *c, const svslam_bm_params *p, BmParams &P)
+{
+    if (!p) return fail(c, "stereo_bm: null parameters");
+    if (p->num_disparities <= 0 || (p->num_disparities & 15) || p->num_disparities > 256)
+        return fail(c, "stereo_bm: num_disparities %d must be a positive multiple of 16, <= 256", p->num_disparities);
+    if (!(p->block_size & 1) || p->block_size < 5 || p->block_size > 21) return fail(c, "stereo_bm: block_size %d must be odd and in [5, 21]", p->block_size);
+    if (p->pre_filter_cap < 1 || p->pre_filter_cap > 63) return fail(c, "stereo_bm: pre_filter_cap %d out of [1, 63]", p->pre_filter_cap);
+    if (p->texture_threshold < 0 || p->uniqueness_ratio < 0) return fail(c, "stereo_bm: texture_threshold %d / uniqueness_ratio %d must not be negative", p->texture_threshold, p->uniqueness_ratio);
+    // (uniqueness_ratio stays an int product: minsad <= 21 * 21 * 126)
+    if (p->uniqueness_ratio > 10000) return fail(c, "stereo_bm: uniqueness_ratio %d > 10000", p->uniqueness_ratio);
+    P.nd = p->num_disparities; P.bs = p->block_size; P.cap = p->pre_filter_cap; P.tex_thr = p->texture_threshold; P.uniq = p->uniqueness_ratio;
+    return 0;
+}
+
+// rows per strip of k_stereo_bm: 16 amortise the 2r+1 rows a strip starts with; a call of few jobs takes shorter strips (8, 4) to
+// fill the device.  0 on stereobm.cpp's early-out (no column or no row to compute: every pixel FILTERED)
+static int bm_strip_rows(int w, int h, int njobs, const BmParams &P)
+{
+    const int r = P.bs / 2, x0 = P.nd - 1 + r, x1 = w - r, y0 = r, y1 = h - r;
+    if (x0 >= x1 || h < 2 * r + 1) return 0;
+    const int tiles = cdiv(x1 - x0, BM_TW);
+    int th = 16;
+    while (th > 4 && (long long)tiles * cdiv(y1 - y0, th) * njobs < 1024) th >>= 1;
+    return th;
+}
+
+int svslam_stereo_bm_strip_rows(svslam_ctx *c, int njobs, const svslam_bm_params *p)
+{
+    if (!c) return -1;
+    BmParams P;
+    if (bm_check_params(c, p, P)) return -1;
+    if (njobs <= 0 || njobs > c->lim.max_jobs) return fail(c, "stereo_bm: %d jobs out of [1, max_jobs]", njobs);
+    return bm_strip_rows(c->geom.w[0], c->geom.h[0], njobs, P);
+}
+
+// enqueue the matcher for njobs jobs (device array djobs) into c->bm.disp; no-op arithmetic when OpenCV's early-out applies
+static int launch_stereo_bm(svslam_ctx *c, int njobs, const BmJob *djobs, const BmParams &P)
+{
+    const int w = c->geom.w[0], h = c->geom.h[0], r = P.bs / 2;
+    if (!c->bm.disp) HIPCHK(c, hipMalloc(&c->bm.disp, sizeof(int16_t) * (size_t)w * h * c->lim.max_jobs));
+    const int x0 = P.nd - 1 + r, x1 = w - r, y0 = r, y1 = h - r;
+    const int th = bm_strip_rows(w, h, njobs, P);
+    const bool none = th == 0;
+    const size_t n = (size_t)w * h * njobs;
+    hipLaunchKernelGGL(k_bm_fill, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->stream, c->bm.disp, w, h, njobs,
+                       none ? 0 : x0, none ? 0 : x1, none ? 0 : y0, none ? 0 : y1);
+    if (!none) {
+        const dim3 grid(cdiv(x1 - x0, BM_TW), cdiv(y1 - y0, th), njobs);
+        const size_t lds = bm_lds_bytes(P.nd, P.bs, th);
+        switch ((P.bs + 3) / 4) {
+        case 2: hipLaunchKernelGGL(k_stereo_bm<2>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
+        case 3: hipLaunchKernelGGL(k_stereo_bm<3>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
+        case 4: hipLaunchKernelGGL(k_stereo_bm<4>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
+        case 5: hipLaunchKernelGGL(k_stereo_bm<5>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
+        default: hipLaunchKernelGGL(k_stereo_bm<6>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+int svslam_stereo_bm_batch(svslam_ctx *c, int njobs, const svslam_bm_job *jobs, const svslam_bm_params *p, int16_t *out_disp)
+{
+    if (!c) return -1;
+    BmParams P;
+    if (bm_check_params(c, p, P)) return -1;
+    if (njobs <= 0) return 0;
+    if (njobs > c->lim.max_jobs) return fail(c, "stereo_bm: %d jobs > max_jobs", njobs);
+    if (!jobs || !out_disp) return fail(c, "stereo_bm: null jobs / output");
+    for (int i = 0; i < njobs; ++i) if (check_slot(c, jobs[i].slot_left) || check_slot(c, jobs[i].slot_right)) return -1;
+    if (arena_busy(c)) return -1;
+    c->ar.reset();
+    static_assert(sizeof(BmJob) == sizeof(svslam_bm_job), "job layout");
+    const size_t ojobs = c->ar.take(sizeof(BmJob) * njobs);
+    memcpy(hp<void>(c, ojobs), jobs, sizeof(BmJob) * njobs);
+    if (h2d(c, 0, c->ar.off)) return -1;
+    tm_begin(c, FAM_BM, njobs);
+    const int rc = launch_stereo_bm(c, njobs, dp<BmJob>(c, ojobs), P);
+    tm_end(c);
+    if (rc) return -1;
+    HIPCHK(c, hipMemcpyAsync(out_disp, c->bm.disp, sizeof(int16_t) * (size_t)c->geom.w[0] * c->geom.h[0] * njobs, hipMemcpyDeviceToHost, c->stream));
+    if (d2h_sync(c, 0, 0)) return -1;
+    return 0;
+}
+
+int svslam_dense_cloud_batch(svslam_ctx *c, int njobs, svslam_dense_job *jobs, const double cam_l[4], const double ext_l[7], double baseline,
+                             const svslam_bm_params *p, double min_depth, int max_pts_per_job, float *out_xyz, int *out_pix,
+                             int16_t *out_disp_or_null)
+{
+    if (!c) return -1;
+    BmParams P;
+    if (bm_check_params(c, p, P)) return -1;
+    if (njobs <= 0) return 0;
+    if (njobs > c->lim.max_jobs) return fail(c, "dense_cloud: %d jobs > max_jobs", njobs);
+    if (!jobs || !cam_l || !ext_l || !out_xyz || !out_pix) return fail(c, "dense_cloud: null argument");
+    if (max_pts_per_job < 1) return fail(c, "dense_cloud: max_pts_per_job %d < 1", max_pts_per_job);
+    if (!(cam_l[0] > 0) || !(cam_l[1] > 0) || !(baseline > 0) || !(min_depth > 0)) return fail(c, "dense_cloud: fx, fy, baseline and min_depth must be positive");
+    for (int i = 0; i < njobs; ++i) {
+        if (check_slot(c, jobs[i].slot_left) || check_slot(c, jobs[i].slot_right)) return -1;
+        if (jobs[i].pt_ofs < 0) return fail(c, "dense_cloud: job %d: negative pt_ofs", i);
+    }
+    if (arena_busy(c)) return -1;
+    const int w = c->geom.w[0], h = c->geom.h[0];
+    const size_t N = (size_t)w * h;
+    const int cap = (int)std::min<size_t>((size_t)max_pts_per_job, N);     // a job has at most w h survivors
+    if (!c->bm.xyz) HIPCHK(c, hipMalloc(&c->bm.xyz, sizeof(float) * 3 * N * c->lim.max_jobs));
+    if (!c->bm.pix) HIPCHK(c, hipMalloc(&c->bm.pix, sizeof(int) * N * c->lim.max_jobs));
+    c->ar.reset();
+    static_assert(sizeof(DenseJob) == sizeof(svslam_dense_job), "job layout");
+    const size_t obm = c->ar.take(sizeof(BmJob) * njobs);
+    const size_t oj = c->ar.take(sizeof(DenseJob) * njobs);
+    for (int i = 0; i < njobs; ++i) { hp<BmJob>(c, obm)[i].slot_left = jobs[i].slot_left; hp<BmJob>(c, obm)[i].slot_right = jobs[i].slot_right; }
+    memcpy(hp<void>(c, oj), jobs, sizeof(DenseJob) * njobs);
+    if (h2d(c, 0, c->ar.off)) return -1;
+    DenseCam cam;
+    cam.fx = cam_l[0]; cam.fy = cam_l[1]; cam.cx = cam_l[2]; cam.cy = cam_l[3];
+    memcpy(cam.ext, ext_l, 56);
+    cam.min_depth = min_depth;
+    cam.fxb = (float)cam_l[0] * (float)baseline;       // focal_length * baseline, both float (src/dense_reconstruction.cpp:120-124, 135)
+    tm_begin(c, FAM_BM, njobs);
+    const int rc = launch_stereo_bm(c, njobs, dp<BmJob>(c, obm), P);
+    if (!rc) hipLaunchKernelGGL(k_dense_cloud, dim3(njobs), dim3(DC_THREADS), 0, c->stream, dp<DenseJob>(c, oj), c->bm.disp, w, h, cam, cap, c->bm.xyz, c->bm.pix);
+    tm_end(c);
+    if (rc) return -1;
+    HIPCHK(c, hipGetLastError());
+    if (d2h_sync(c, oj, oj + sizeof(DenseJob) * njobs)) return -1;
+    for (int i = 0; i < njobs; ++i) {
+        jobs[i].n_points = hp<DenseJob>(c, oj)[i].n_points;
+        if (jobs[i].n_points > max_pts_per_job) return fail(c, "dense_cloud: job %d has %d points > max_pts_per_job %d", i, jobs[i].n_points, max_pts_per_job);
+    }
+    for (int i = 0; i < njobs; ++i) {
+        const size_t n = (size_t)jobs[i].n_points;
+        if (!n) continue;
+        HIPCHK(c, hipMemcpy(out_xyz + 3 * (size_t)jobs[i].pt_ofs, c->bm.xyz + 3 * (size_t)i * cap, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(out_pix + (size_t)jobs[i].pt_ofs, c->bm.pix + (size_t)i * cap, sizeof(int) * n, hipMemcpyDeviceToHost));
+    }
+    if (out_disp_or_null) HIPCHK(c, hipMemcpy(out_disp_or_null, c->bm.disp, sizeof(int16_t) * N * njobs, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ------------------------------------------------------------------ cloud filters (src/dense_reconstruction.cpp:175-209)
+// a cloud-filter buffer of at least `bytes`; a regrow takes a quarter of headroom plus 256 bytes
+static int cf_reserve(svslam_ctx *c, DevBuf &b, size_t bytes) { return b.reserve(c, "cloud_filter", bytes, bytes / 4 + 256); }
+static inline dim3 cf_grid(long long n) { return dim3((unsigned)((n + CF_THREADS - 1) / CF_THREADS)); }
+
+int svslam_cloud_sor_batch(svslam_ctx *c, int nseg, const int64_t *seg_ofs, const float *xyz, int mean_k, double stddev_mul, uint8_t *out_keep,
+                           float *out_mean_dist_or_null, double *out_threshold)
+{
+    if (!c) return -1;
+    if (mean_k < 1 || mean_k > CF_KMAX) return fail(c, "cloud_filter: mean_k %d out of [1, %d]", mean_k, CF_KMAX);
+    if (nseg < 0) return fail(c, "cloud_filter: %d segments", nseg);
+    if (nseg == 0) return 0;
+    if (!seg_ofs || !out_threshold) return fail(c, "cloud_filter: null seg_ofs / out_threshold");
+    for (int s = 0; s < nseg; ++s) if (seg_ofs[s + 1] < seg_ofs[s] || seg_ofs[s] < 0) return fail(c, "cloud_filter: seg_ofs must be non-negative and ascending (segment %d)", s);
+    const int64_t first = seg_ofs[0], total64 = seg_ofs[nseg] - first;
+    if (total64 > (int64_t)1 << 30) return fail(c, "cloud_filter: %lld points in one call > 2^30", (long long)total64);
+    if (nseg > 1 << 20) return fail(c, "cloud_filter: %d segments > 2^20", nseg);
+    const int total = (int)total64;
+    if (total && (!xyz || !out_keep)) return fail(c, "cloud_filter: null xyz / out_keep");
+    // one host pass: every coordinate finite (PCL's branch for the others is not restated), the box of every segment
+    std::vector<CfSeg> segs((size_t)nseg);
+    bool any = false;
+    for (int s = 0; s < nseg; ++s) {
+        CfSeg &g = segs[(size_t)s];
+        g.ofs = (int)(seg_ofs[s] - first); g.n = (int)(seg_ofs[s + 1] - seg_ofs[s]); g.pad = 0;
+        float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
+        const float *p = xyz + 3 * (size_t)seg_ofs[s];
+        for (int i = 0; i < g.n; ++i, p += 3) {
+            if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]))
+                return fail(c, "cloud_filter: point %d of segment %d has a non-finite coordinate", i, s);
+            for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], p[a]); mx[a] = std::max(mx[a], p[a]); }
+        }
+        float ext = 0.f;
+        for (int a = 0; a < 3; ++a) { g.mn[a] = g.n ? mn[a] : 0.f; if (g.n) ext = std::max(ext, mx[a] - mn[a]); }
+        g.inv_h = ext > 0.f ? 1024.0f / ext : 0.f;
+        if (!std::isfinite(g.inv_h)) g.inv_h = 0.f;
+        g.h = g.inv_h > 0.f ? 1.0f / g.inv_h : 0.f;
+        any = any || g.n >= mean_k + 1;
+    }
+    std::vector<float> md_own;
+    if (!out_mean_dist_or_null) md_own.resize((size_t)std::max(total, 1));
+    float *mdv = out_mean_dist_or_null ? out_mean_dist_or_null + first : md_own.data();       // mean distance of point seg_ofs[0] + i
+    if (!any) std::fill(mdv, mdv + total, 0.f);
+    else {
+        const size_t N = (size_t)total;
+        auto &f = c->cf;
+        if (cf_reserve(c, f.xyz, 12 * N) || cf_reserve(c, f.segs, sizeof(CfSeg) * (size_t)nseg) || cf_reserve(c, f.keys, 8 * N) || cf_reserve(c, f.keys2, 8 * N) ||
+            cf_reserve(c, f.vals, 4 * N) || cf_reserve(c, f.vals2, 4 * N) || cf_reserve(c, f.soa, 12 * N) || cf_reserve(c, f.out, 4 * N)) return -1;
+        if (!f.climbs) { HIPCHK(c, hipMalloc(&f.climbs, sizeof(unsigned))); }
+        int seg_bits = 1;
+        while ((1 << seg_bits) < nseg) ++seg_bits;
+        size_t tmp_bytes = 0;
+        HIPCHK(c, rocprim::radix_sort_pairs(nullptr, tmp_bytes, (unsigned long long *)f.keys.d, (unsigned long long *)f.keys2.d, (unsigned *)f.vals.d,
+                                            (unsigned *)f.vals2.d, N, 0u, (unsigned)(30 + seg_bits), c->stream));
+        if (cf_reserve(c, f.tmp, tmp_bytes)) return -1;
+        HIPCHK(c, hipMemcpy(f.xyz.d, xyz + 3 * (size_t)first, 12 * N, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(f.segs.d, segs.data(), sizeof(CfSeg) * (size_t)nseg, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemsetAsync(f.climbs, 0, sizeof(unsigned), c->stream));
+        float *sx = (float *)f.soa.d, *sy = sx + N, *sz = sy + N;
+        tm_begin(c, FAM_CF, total);
+        hipLaunchKernelGGL(k_cf_keys, cf_grid(total), dim3(CF_THREADS), 0, c->stream, (const float *)f.xyz.d, total, (const CfSeg *)f.segs.d, nseg,
+                           (unsigned long long *)f.keys.d, (unsigned *)f.vals.d);
+        HIPCHK(c, rocprim::radix_sort_pairs(f.tmp.d, tmp_bytes, (unsigned long long *)f.keys.d, (unsigned long long *)f.keys2.d, (unsigned *)f.vals.d,
+                                            (unsigned *)f.vals2.d, N, 0u, (unsigned)(30 + seg_bits), c->stream));
+        hipLaunchKernelGGL(k_cf_gather, cf_grid(total), dim3(CF_THREADS), 0, c->stream, (const float *)f.xyz.d, (const unsigned *)f.vals2.d, total, sx, sy, sz);
+        // 51 register slots hold the reference's k = 50; a larger k takes the 65-slot instance
+        if (mean_k <= 50)
+            hipLaunchKernelGGL(k_cf_knn<51>, cf_grid(total), dim3(CF_THREADS), 0, c->stream, (const unsigned long long *)f.keys2.d, (const unsigned *)f.vals2.d,
+                               (const float *)sx, (const float *)sy, (const float *)sz, total, (const CfSeg *)f.segs.d, mean_k, (float *)f.out.d, f.climbs);
+        else
+            hipLaunchKernelGGL(k_cf_knn<CF_KMAX + 1>, cf_grid(total), dim3(CF_THREADS), 0, c->stream, (const unsigned long long *)f.keys2.d, (const unsigned *)f.vals2.d,
+                               (const float *)sx, (const float *)sy, (const float *)sz, total, (const CfSeg *)f.segs.d, mean_k, (float *)f.out.d, f.climbs);
+        tm_end(c);
+        HIPCHK(c, hipGetLastError());
+        if (d2h_sync(c, 0, 0)) return -1;
+        HIPCHK(c, hipMemcpy(mdv, f.out.d, 4 * N, hipMemcpyDeviceToHost));
+        unsigned climbed = 0;
+        HIPCHK(c, hipMemcpy(&climbed, f.climbs, sizeof(unsigned), hipMemcpyDeviceToHost));
+        for (const CfSeg &g : segs) if (g.n >= mean_k + 1) f.queries += g.n;
+        f.climbed += climbed;
+    }
+    // PCL's statistics on the host, sequentially in index order: the threshold has the yardstick's bits by construction
+    for (int s = 0; s < nseg; ++s) {
+        const CfSeg &g = segs[(size_t)s];
+        const float *d = mdv + g.ofs;
+        uint8_t *keep = out_keep + seg_ofs[s];
+        if (g.n < mean_k + 1) {                            // no valid distance: 0 / 0, nothing is above a NaN
+            out_threshold[s] = std::nan("");
+            for (int i = 0; i < g.n; ++i) keep[i] = 1;
+            continue;
+        }
+        double sum = 0.0, sq_sum = 0.0;
+        for (int i = 0; i < g.n; ++i) { sum += (double)d[i]; const float sq = d[i] * d[i]; sq_sum += (double)sq; }
+        const double nv = (double)g.n, mean = sum / nv, var = (sq_sum - sum * sum / nv) / (nv - 1.0);
+        const double thr = mean + stddev_mul * std::sqrt(var);
+        out_threshold[s] = thr;
+        for (int i = 0; i < g.n; ++i) keep[i] = !((double)d[i] > thr) ? 1 : 0;
+    }
+    return 0;
+}
+
+int svslam_debug_cloud_sor_climbs(svslam_ctx *c, long long *out_queries, long long *out_climbed)
+{
+    if (!c) return -1;
+    if (out_queries) *out_queries = c->cf.queries;
+    if (out_climbed) *out_climbed = c->cf.climbed;
+    c->cf.queries = c->cf.climbed = 0;
+    return 0;
+}
+
+int svslam_cloud_voxel_grid(svslam_ctx *c, int64_t n, const float *xyz, const uint8_t *rgb, double leaf, float *out_xyz, uint8_t *out_rgb,
+                            int64_t *out_n, int *out_overflowed)
+{
+    if (!c) return -1;
+    if (!(leaf > 0) || !std::isfinite(leaf)) return fail(c, "cloud_filter: leaf %g must be positive", leaf);
+    if (n < 0 || n > (int64_t)1 << 30) return fail(c, "cloud_filter: %lld points out of [0, 2^30]", (long long)n);
+    if (!out_n || !out_overflowed) return fail(c, "cloud_filter: null out_n / out_overflowed");
+    *out_n = 0; *out_overflowed = 0;
+    if (n == 0) return 0;
+    if (!xyz || !rgb || !out_xyz || !out_rgb) return fail(c, "cloud_filter: null cloud / output");
+    const size_t N = (size_t)n;
+    float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for (size_t i = 0; i < N; ++i)
+        for (int a = 0; a < 3; ++a) {
+            const float v = xyz[3 * i + a];
+            if (!std::isfinite(v)) return fail(c, "cloud_filter: point %zu has a non-finite coordinate", i);
+            mn[a] = std::min(mn[a], v); mx[a] = std::max(mx[a], v);
+        }
+    VgParams P;
+    P.inv = 1.0f / (float)leaf;
+    if (!std::isfinite(P.inv) || !(P.inv > 0.f)) return fail(c, "cloud_filter: leaf %g has no float reciprocal", leaf);
+    // PCL's guard: more than INT32_MAX cells -> "Leaf size is too small for the input dataset", the output is the input
+    int64_t cells[3];
+    bool over = false;
+    for (int a = 0; a < 3; ++a) {
+        const float e = (mx[a] - mn[a]) * P.inv;
+        if (!(e < 9.0e18f)) over = true; else cells[a] = (int64_t)e + 1;
+    }
+    if (!over) over = (__int128)cells[0] * cells[1] * cells[2] > (__int128)INT32_MAX;
+    if (over) {
+        memcpy(out_xyz, xyz, 12 * N); memcpy(out_rgb, rgb, 3 * N);
+        *out_n = n; *out_overflowed = 1;
+        return 0;
+    }
+    int max_b[3], div_b[3];
+    for (int a = 0; a < 3; ++a) {
+        P.min_b[a] = (int)std::floor(mn[a] * P.inv); max_b[a] = (int)std::floor(mx[a] * P.inv);
+        div_b[a] = max_b[a] - P.min_b[a] + 1;
+    }
+    P.mul[0] = 1; P.mul[1] = div_b[0]; P.mul[2] = (int)((unsigned)div_b[0] * (unsigned)div_b[1]);
+    auto &f = c->cf;
+    if (cf_reserve(c, f.xyz, 12 * N) || cf_reserve(c, f.rgb, 3 * N) || cf_reserve(c, f.keys, 8 * N) || cf_reserve(c, f.keys2, 8 * N) || cf_reserve(c, f.flag, 4 * N) ||
+        cf_reserve(c, f.pos, 4 * N) || cf_reserve(c, f.start, 4 * N) || cf_reserve(c, f.oxyz, 12 * N) || cf_reserve(c, f.orgb, 3 * N)) return -1;
+    size_t sort_bytes = 0, scan_bytes = 0;
+    HIPCHK(c, rocprim::radix_sort_keys(nullptr, sort_bytes, (unsigned long long *)f.keys.d, (unsigned long long *)f.keys2.d, N, 0u, 64u, c->stream));
+    HIPCHK(c, rocprim::inclusive_scan(nullptr, scan_bytes, (unsigned *)f.flag.d, (unsigned *)f.pos.d, N, rocprim::plus<unsigned>(), c->stream));
+    if (cf_reserve(c, f.tmp, std::max(sort_bytes, scan_bytes))) return -1;
+    HIPCHK(c, hipMemcpy(f.xyz.d, xyz, 12 * N, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(f.rgb.d, rgb, 3 * N, hipMemcpyHostToDevice));
+    const int ni = (int)n;
+    tm_begin(c, FAM_CF, n);
+    hipLaunchKernelGGL(k_vg_keys, cf_grid(n), dim3(CF_THREADS), 0, c->stream, (const float *)f.xyz.d, ni, P, (unsigned long long *)f.keys.d);
+    HIPCHK(c, rocprim::radix_sort_keys(f.tmp.d, sort_bytes, (unsigned long long *)f.keys.d, (unsigned long long *)f.keys2.d, N, 0u, 64u, c->stream));
+    hipLaunchKernelGGL(k_vg_heads, cf_grid(n), dim3(CF_THREADS), 0, c->stream, (const unsigned long long *)f.keys2.d, ni, (unsigned *)f.flag.d);
+    HIPCHK(c, rocprim::inclusive_scan(f.tmp.d, scan_bytes, (unsigned *)f.flag.d, (unsigned *)f.pos.d, N, rocprim::plus<unsigned>(), c->stream));
+    hipLaunchKernelGGL(k_vg_starts, cf_grid(n), dim3(CF_THREADS), 0, c->stream, (const unsigned *)f.flag.d, (const unsigned *)f.pos.d, ni, (int *)f.start.d);
+    HIPCHK(c, hipGetLastError());
+    // the number of voxels decides the last launch: one small read-back in the middle of the call
+    unsigned m = 0;
+    HIPCHK(c, hipMemcpyAsync(&m, (unsigned *)f.pos.d + (N - 1), sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (m < 1 || (size_t)m > N) return fail(c, "cloud_filter: voxel count %u out of [1, %zu]", m, N);
+    hipLaunchKernelGGL(k_vg_reduce, cf_grid(m), dim3(CF_THREADS), 0, c->stream, (const unsigned long long *)f.keys2.d, (const int *)f.start.d, (int)m, ni,
+                       (const float *)f.xyz.d, (const uint8_t *)f.rgb.d, (float *)f.oxyz.d, (uint8_t *)f.orgb.d);
+    tm_end(c);
+    HIPCHK(c, hipGetLastError());
+    if (d2h_sync(c, 0, 0)) return -1;
+    HIPCHK(c, hipMemcpy(out_xyz, f.oxyz.d, 12 * (size_t)m, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out_rgb, f.orgb.d, 3 * (size_t)m, hipMemcpyDeviceToHost));
+    *out_n = (int64_t)m;
+    return 0;
+}
+
+} // extern "C"

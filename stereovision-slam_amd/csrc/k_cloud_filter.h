@@ -4,7 +4,7 @@
 //   pcl::VoxelGrid                   voxel index per point, run heads of the sorted (index, point) keys, one thread per voxel
 //                                    summing its run in point order (k_vg_keys, k_vg_heads, k_vg_starts, k_vg_reduce)
 // The numeric contract is tests/ref_cloud_filters.py.  The two sorts between the kernels are rocPRIM's, called from
-// svslam_hip.hip: this file has no library in it and no cross-lane operation, so tests/cpp/cf_host_emu runs it on the host.
+// api_dense.h: this file has no library in it and no cross-lane operation, so tests/cpp/cf_host_emu runs it on the host.
 //
 // kNN.  Points get a 30-bit Morton key (10 bits per axis) over their segment's bounding box, in cubic cells of side h = largest
 // extent / 1024; the key's upper bits hold the segment, so one sort orders a whole batch.  A query (one per lane, in sorted

@@ -26,7 +26,7 @@ The constants below restate csrc/k_ba.h and csrc/k_ba_build.h.  Whoever changes 
   the dealing rule (ll_deal)                                                                   k_ba_build.h:327-332, 386-396
   what k_ba_build does for a shard (structure(no_group, all_active))                           k_ba_build.h:150-151, 172-173
   ll_shard_in_lds                                                                              k_ba.h "const bool ll_res"
-  ll_enabled, ll_tile_cap                                         svslam_hip.hip svslam_set_low_latency, ba_ll_tile_cap
+  ll_enabled, ll_tile_cap                             api_ba.h svslam_set_low_latency, svslam_hip.hip ba_ll_tile_cap
 """
 import numpy as np
 

@@ -4,6 +4,7 @@ the same bits; a job giving the same result alone and among others; Context.brie
 import numpy as np
 import pytest
 
+import global_desc_cases as gc     # new_context, settle_rotation: the contexts made here leave the stream rotation as it was
 import brief_cases as bc
 import ref_brief as rb
 
@@ -75,6 +76,31 @@ def test_two_calls_same_bits_and_a_job_alone_or_among_others(contexts):
         alone = bc.abi_call(dict(c, jobs=[(slot, 0, n)], xy=c["xy"][o:o + n]), ctx=ctx)
         k = together[2][i]
         assert alone[2] == [k] and np.array_equal(alone[3][:k], together[3][o:o + k]) and np.array_equal(alone[4][:k], together[4][o:o + k])
+
+
+def test_the_kept_buffer_carries_nothing_over(svs):
+    """on a fresh context: npts_1, npts_63, npts_1 again.  br_layout takes, rounded up to 16 each, 16 n + 8 n + 1024 (the table) +
+    16 jobs + 4 n + 32 n: 1120 bytes for one point of one job (the context then keeps 1400) and 4832 for 63 points, more than
+    1.25 * 1120 + 256 = 1656, so the second call replaces the buffer and the third runs in what the second left there.  The first and
+    third results are the same bits, and the bits of the case on a context that has seen nothing else; every call is the reference's."""
+    small, big = bc.case("npts_1"), bc.case("npts_63")
+    assert small["size"] == big["size"] == "620x188" and small["kind"] == big["kind"]
+    w, h = bc.SIZES["620x188"]
+    a = gc.new_context(svs, w, h, max_slots=bc.NSLOTS, max_jobs=bc.NSLOTS)
+    b = gc.new_context(svs, w, h, max_slots=bc.NSLOTS, max_jobs=bc.NSLOTS)
+    try:
+        for c in (a, b):
+            c.pyramid(list(range(bc.NSLOTS)), list(bc.images("620x188", small["kind"])))
+        first, second, third = bc.abi_call(small, ctx=a), bc.abi_call(big, ctx=a), bc.abi_call(small, ctx=a)
+        alone = bc.abi_call(small, ctx=b)
+    finally:
+        a.close(); b.close(); gc.settle_rotation(svs)
+    for c, name, res in ((small, "npts_1", first), (big, "npts_63", second), (small, "npts_1", third), (small, "npts_1", alone)):
+        ok, msg = bc.compare(c, bc.reference(name), res)
+        assert ok, (name, msg)
+    assert first[2] == [1] and second[2][0] > 1
+    for res in (third, alone):
+        assert res[2] == first[2] and np.array_equal(res[3], first[3]) and np.array_equal(res[4], first[4])
 
 
 def test_python_interface_and_timing_family(contexts):

@@ -8,6 +8,7 @@ import math
 import numpy as np
 import pytest
 
+import global_desc_cases as gc     # new_context, settle_rotation: the contexts made here leave the stream rotation as it was
 import ref_cloud_filters as rcf
 from cloud_filter_cases import BASELINE, CAM, IDENT, POSE, depth_crop, sor_cases, voxel_cases
 
@@ -140,6 +141,32 @@ def test_voxel_grid_overflow_returns_the_input(ctx, depth):
         assert ctx.cloud_voxel_grid(xyz, rgb[:2], 1.0)[2] is want
     # the context goes on working after the early return
     _vg_same(ctx, depth[0], depth[1], 0.5, "after")
+
+
+def test_the_kept_buffers_carry_nothing_over(svs):
+    """on a fresh context: both filters on n51 (mean_k + 1 points), on the first 204 points of n1000, on n51 again.  Every buffer of
+    the family holds a fixed number of bytes per point (12 xyz, 8 a key, 4 a value or a distance, 3 a colour) and a regrow takes a
+    quarter plus 256 bytes more: 51 points ask for 612, 408, 204 and 153 bytes (the context then keeps 1021, 766, 511 and 447), 204
+    points for 2448, 1632, 816 and 612, each more than 1.25 times the first request plus 256, so the second round replaces every
+    per-point buffer and the third runs in what it left.  First and third round are the same bits, the bits of a context that has
+    seen nothing else, and the restatement's."""
+    c = sor_cases(svs, depth=False)
+    small, big = c["n51"], np.ascontiguousarray(c["n1000"][:204])
+    rgb = np.random.default_rng(3).integers(0, 256, (204, 3)).astype(np.uint8)
+    a = gc.new_context(svs, 64, 32, max_slots=1, max_jobs=1, **KW)
+    b = gc.new_context(svs, 64, 32, max_slots=1, max_jobs=1, **KW)
+    try:
+        rounds = [(x.cloud_sor([p])[0], x.cloud_voxel_grid(p, rgb[:len(p)], 0.5)) for x, p in ((a, small), (a, big), (a, small), (b, small))]
+    finally:
+        a.close(); b.close(); gc.settle_rotation(svs)
+    for (sor, vg), p in zip(rounds, (small, big, small, small)):
+        _same(sor, rcf.sor(p), len(p))
+        assert not math.isnan(sor[2])
+        wx, wr, wover = rcf.voxel_grid(p, rgb[:len(p)], 0.5)
+        assert vg[2] == wover and np.array_equal(vg[0], wx) and np.array_equal(vg[1], wr) and 1 < len(wx) < len(p)
+    for sor, vg in rounds[2:]:
+        _same(sor, rounds[0][0], "again")
+        assert all(np.array_equal(x, y) for x, y in zip(vg[:2], rounds[0][1][:2]))
 
 
 def test_argument_errors_leave_the_context_usable(ctx, cases, refs):

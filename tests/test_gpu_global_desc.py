@@ -104,6 +104,35 @@ def test_chunks_of_one_job_on_the_tiny_net(ctx):
     assert np.array_equal(gc.bits(dev[0]), gc.bits(dev[4])) and np.array_equal(gc.bits(dev[2]), gc.bits(dev[3]))
 
 
+def test_the_kept_buffers_carry_nothing_over(svs):
+    """on a fresh context with the tiny net (dim 5): 1 job, 20 jobs, 1 job.  The slots / vectors buffer takes 4 n rounded up to 256,
+    then 20 n bytes: 276 for one job (the context then keeps 345) and 656 for 20, more than 1.25 * 276 + 256 = 601.  The workspace
+    takes 4 * job_floats bytes per job of the chunk and no headroom; all 20 jobs are one chunk, and a job's share holds at least the
+    3 x 16 x 16 blob, so 20 shares pass 1.25 shares + 256 bytes.  The second call replaces both buffers, the third runs in what it
+    left: first and third are the same bits, the bits of a context that has seen nothing else, and the host build's."""
+    layers, out_wh = gc.tiny_net()
+    prm, prep = gc.seeded(layers, 3), gc.case_prep(out_wh)
+    many = [i % gc.NSLOTS for i in range(20)]
+    rc, msg = gc.emu_configure(SRC[0], SRC[1], layers, prm, prep)
+    assert rc == 0, msg
+    assert 20 * 4 * gc.load_emu().emu_gd_job_floats() <= 256 << 20 and gc.load_emu().emu_gd_job_floats() >= 3 * 16 * 16
+    host = gc.emu_describe(gc.images(*SRC), many)
+    assert host["rc"] == 0, host["msg"]
+    a = gc.new_context(svs, SRC[0], SRC[1], max_slots=gc.NSLOTS, max_jobs=gc.NSLOTS)
+    b = gc.new_context(svs, SRC[0], SRC[1], max_slots=gc.NSLOTS, max_jobs=gc.NSLOTS)
+    try:
+        for c in (a, b):
+            c.pyramid(list(range(gc.NSLOTS)), list(gc.images(*SRC)))
+            c.gdesc_configure(layers, prm, prep)
+        first, big, third = a.gdesc_describe([0]), a.gdesc_describe(many), a.gdesc_describe([0])
+        alone = b.gdesc_describe([0])
+    finally:
+        a.close(); b.close()
+    same(big, host["vecs"])
+    same(first, host["vecs"][:1])
+    assert np.array_equal(gc.bits(third), gc.bits(first)) and np.array_equal(gc.bits(alone), gc.bits(first))
+
+
 def test_unconfigured_context_refuses(svs):
     c = gc.new_context(svs, 32, 32, max_slots=2, max_jobs=2)
     try:

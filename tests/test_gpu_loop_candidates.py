@@ -4,6 +4,7 @@ of every stored row; then Context's methods and the timing family."""
 import numpy as np
 import pytest
 
+import global_desc_cases as gc     # new_context, settle_rotation: the contexts made here leave the stream rotation as it was
 import loop_candidates_cases as lc
 import ref_loop_candidates as rl
 
@@ -20,6 +21,37 @@ def drv(svs):
 @pytest.mark.parametrize("name", list(lc.CASES))
 def test_against_the_reference(svs, drv, name):
     print(name, lc.check(name, drv))
+
+
+def test_the_kept_staging_carries_nothing_over(svs):
+    """on a fresh context with two streams of dim 128: one row appended to stream 0 and one query of it, eight rows appended to stream
+    1, the query of stream 0 again.  A call stages its structs rounded up to 256 bytes, then 512 bytes per vector: 256 + 512 = 768
+    bytes for the one-row append and for the query (the context then keeps 960), 256 + 8 * 512 = 4352 for the eight rows, more than
+    1.25 * 768 + 256 = 1216, so that append replaces the buffer and the second query runs in what it left there.  Both queries give
+    the same bits, the bits of a context that has seen only the first append, and the reference's; the eight rows are stored right."""
+    dim = 128
+    one, eight, ids8 = lc.vecs(61, 1, dim), lc.vecs(62, 8, dim), list(range(3, 27, 3))
+    q = lc.near(one[0], 3, 0.005)[None]
+    key = lambda g: (g["status"], g["cand_kf"], lc.bits(g["best_sim"]), g["best_kf"], g["n_weak"], g["n_compared"])
+    ref = rl.Store(); ref.configure(2, 8, dim)
+    assert ref.append([0], [2], one) is None and ref.append([1] * 8, ids8, eight) is None
+    (want,) = ref.candidates([(0, 120)], q)
+    a = gc.new_context(svs, 64, 48, max_slots=1, max_jobs=1)
+    b = gc.new_context(svs, 64, 48, max_slots=1, max_jobs=1)
+    try:
+        for c in (a, b):
+            c.loopdb_configure(2, 8, dim)
+            c.loopdb_append([0], [2], one)
+        (first,) = a.loop_candidates([(0, 120)], q)
+        a.loopdb_append([1] * 8, ids8, eight)
+        (third,) = a.loop_candidates([(0, 120)], q)
+        (alone,) = b.loop_candidates([(0, 120)], q)
+        ids, rows = a.loopdb_read(1)
+    finally:
+        a.close(); b.close(); gc.settle_rotation(svs)
+    assert key(first) == key(third) == key(alone) == lc._result(want) and first["n_compared"] == 1 and first["status"] == rl.FOUND
+    rid, rrows = ref.read(1)
+    assert np.array_equal(ids, rid) and np.array_equal(rows.view(np.uint32), rrows.view(np.uint32))
 
 
 def test_python_interface_and_timing_family(svs):

@@ -4,6 +4,7 @@ q 1e-7), d within 1e-6; the ABI's refusals; independence of the jobs of a call a
 import numpy as np
 import pytest
 
+import global_desc_cases as gc     # new_context, settle_rotation: the contexts made here leave the stream rotation as it was
 import loop_verify_cases as lc
 import ref_loop_verify as rl
 
@@ -40,6 +41,27 @@ def test_batch_independence_and_determinism(ctx):
         assert lc.same_bits(alone, together[i]) and lc.same_bits(again[i], together[i]), n
         ok, msg = lc.compare(together[i], lc.reference(n))
         assert ok, (n, msg)
+
+
+def test_the_kept_buffer_carries_nothing_over(svs):
+    """on a fresh context: small_412_5, n64_64, small_412_5 again.  lv_layout takes 272 bytes for the job and, rounded up to 16 each,
+    3 * 4 nc + nc + 32 nc + 32 nq + 12 nc + 8 nq + nc: 832 bytes for 5 x 5 descriptors (the context then keeps 1040) and 6544 for
+    64 x 64, more than 1.25 * 832 + 256 = 1296, so the second call replaces the buffer and the third runs in what the second left
+    there.  The first and third results are the same bits, and the bits of the case on a context that has seen nothing else."""
+    small, p = lc.case("small_412_5"), lc.params("small_412_5")
+    a = gc.new_context(svs, 64, 32, max_slots=1, max_jobs=1)
+    b = gc.new_context(svs, 64, 32, max_slots=1, max_jobs=1)
+    try:
+        (first,) = a.loop_verify([small], lc.CAM, lc.EXT_L, **p)
+        (big,) = a.loop_verify([lc.case("n64_64")], lc.CAM, lc.EXT_L)
+        (third,) = a.loop_verify([small], lc.CAM, lc.EXT_L, **p)
+        (alone,) = b.loop_verify([small], lc.CAM, lc.EXT_L, **p)
+    finally:
+        a.close(); b.close(); gc.settle_rotation(svs)
+    assert first["status"] == rl.ACCEPTED and big["status"] == rl.ACCEPTED
+    assert lc.same_bits(first, third) and lc.same_bits(first, alone)
+    ok, msg = lc.compare(big, lc.reference("n64_64"))
+    assert ok, msg
 
 
 def test_refusals_write_nothing(ctx, svs):
