@@ -170,7 +170,8 @@ int svslam_gftt_eigmap(svslam_ctx *ctx, int slot, float *out);
  * An image too small for one window (nd - 1 + r >= w - r, or h < 2 r + 1 with r = block_size / 2)
  * succeeds with every pixel -16, like OpenCV.
  * num_disparities: positive multiple of 16, <= 256; block_size: odd, 5 .. 21; pre_filter_cap: 1 .. 63.
- * Colour input, PREFILTER_NORMALIZED_RESPONSE, the speckle filter and disp12MaxDiff are not built.  */
+ * PREFILTER_NORMALIZED_RESPONSE, the speckle filter and disp12MaxDiff are not built.  Colour input:
+ * svslam_pyramid_bgr_batch and svslam_dense_cloud_bgr_batch, below.                                */
 typedef struct svslam_bm_params {
     int num_disparities;   /* 128 */
     int block_size;        /* 15  */
@@ -195,7 +196,7 @@ int svslam_stereo_bm_strip_rows(svslam_ctx *ctx, int njobs, const svslam_bm_para
  * 39-44, 58-86: T_cw^-1 * ext_l^-1 * pixel2camera) in double and rounded to float (PointXYZRGB).
  * Job i's points are written from out_xyz[3 * pt_ofs] / out_pix[pt_ofs] on in the reference's order —
  * x outer, y inner; out_pix holds y * width + x of each point, for the caller to colour it from the
- * image it holds.  n_points (out) beyond max_pts_per_job is an error, nothing of that call is returned.
+ * image it holds (svslam_dense_cloud_bgr_batch, below, returns the colours itself).  n_points (out) beyond max_pts_per_job is an error, nothing of that call is returned.
  * out_disp_or_null: the disparity maps as svslam_stereo_bm_batch returns them.
  * The StatisticalOutlierRemoval and the VoxelGrid of :175-209 (PCL) are calls of their own, below:
  * svslam_cloud_sor_batch and svslam_cloud_voxel_grid take the clouds this call returned.             */
@@ -210,6 +211,42 @@ int svslam_dense_cloud_batch(svslam_ctx *ctx, int njobs, svslam_dense_job *jobs,
                              const double ext_l[7], double baseline, const svslam_bm_params *p,
                              double min_depth, int max_pts_per_job, float *out_xyz, int *out_pix,
                              int16_t *out_disp_or_null);
+
+/* ---- colour input of run_dense_reconstruction ----------------------------------------------
+ * Every dense config of the reference sets is_color_input: 1: Dataset reads cv::IMREAD_COLOR, DenseReconstruct()
+ * converts both images with cv::cvtColor(COLOR_BGR2GRAY) for the matcher and gives every point the left image's
+ * b, g, r at its pixel (src/dense_reconstruction.cpp:104-171).  BGR is the only byte order: it is the cv::Mat
+ * the reference holds.
+ * The grey of a colour pixel, in integers: the one definition the device kernel (csrc/k_colour.h) and the host
+ * PNG reader (facade::read_png) share.  Parity of these weights with OpenCV's own 8-bit BGR2GRAY is unpinned
+ * (DESIGN 9).                                                                                            */
+#define SVSLAM_GREY_FROM_RGB(r, g, b) (((r) * 4899 + (g) * 9617 + (b) * 1868 + 8192) >> 14)
+
+/* nplanes colour planes of width x height x 3 bytes (b, g, r) on the device; 0 frees them; a new count drops
+ * the contents, the present count keeps them. */
+int svslam_colour_reserve(svslam_ctx *ctx, int nplanes);
+/* n packed 8-bit BGR images (3 bytes per pixel, strides[i] >= 3 * src_w bytes per row, host or device memory)
+ * -> pyramid slots slots[i], built from the grey image exactly as svslam_pyramid_batch builds them from that
+ * grey image, and, where planes[i] >= 0, the working-resolution BGR image into that colour plane (-1: keep no
+ * colour).  src_w x src_h is the context's width x height, or a size that halves to it by
+ * svslam_pyramid_decimate_batch's rule; then dst(x, y) = src(2x, 2y) and only the even source rows are read.
+ * No byte beyond strides[i] * (src_h - 1) + 3 * src_w of a source is read.
+ * Errors, all decided before anything is launched or written: a null pointer, n > max_jobs, a bad slot, a
+ * plane outside [-1, nplanes), a plane named while none is reserved, the same plane named twice, a stride
+ * below 3 * src_w, a source size that is neither the context's nor halves to it.                          */
+int svslam_pyramid_bgr_batch(svslam_ctx *ctx, int n, const int *slots, const int *planes, const void *const *imgs,
+                             const int *strides, int src_w, int src_h, int src_is_device);
+/* test hook: a colour plane, [height][width][3] */
+int svslam_colour_read(svslam_ctx *ctx, int plane, uint8_t *out);
+/* svslam_dense_cloud_batch with the colour of every point: out_bgr holds 3 bytes (b, g, r) per point, indexed
+ * like out_xyz, taken on the device from plane planes[i] of job i at out_pix.  out_xyz, out_pix, n_points and
+ * the disparity maps have the bits svslam_dense_cloud_batch gives for the same slots; the max_pts_per_job rule
+ * is the same.  Further errors, decided before anything is launched: null planes / out_bgr, no planes reserved,
+ * a plane outside [0, nplanes), a plane no upload has written since it was reserved.                       */
+int svslam_dense_cloud_bgr_batch(svslam_ctx *ctx, int njobs, svslam_dense_job *jobs, const double cam_l[4],
+                                 const double ext_l[7], double baseline, const svslam_bm_params *p,
+                                 double min_depth, int max_pts_per_job, const int *planes, float *out_xyz,
+                                 int *out_pix, uint8_t *out_bgr, int16_t *out_disp_or_null);
 
 /* ---- the cloud filters of run_dense_reconstruction -----------------------------------------
  * The numeric contract of both is tests/ref_cloud_filters.py (parity with PCL itself is unpinned).
@@ -788,7 +825,8 @@ int svslam_sync(svslam_ctx *ctx);
  * after the last number in use, nothing moved), 13 pose_graph (units = jobs; appended after 12, nothing moved),
  * 14 loop_verify (units = jobs; appended after 13, nothing moved), 15 brief (units = points; appended after 14, nothing moved),
  * 16 loop_candidates (units = rows compared, summed over the jobs; appended after 15, nothing moved),
- * 17 global_desc (units = jobs; appended after 16, nothing moved).
+ * 17 global_desc (units = jobs; appended after 16, nothing moved),
+ * 18 colour (the conversion kernel of svslam_pyramid_bgr_batch; units = images; appended after 17, nothing moved).
  * Development families follow and are NOT stable numbers: with stereo_bm taking 6, the
  * per-kernel split moved from 6-9 to 7-10 and the local-BA solver interval from 10 to 11.
  * A caller that passed those raw numbers must move with them (Python addresses them by name). */

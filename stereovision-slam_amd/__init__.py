@@ -19,7 +19,8 @@ LIB_DIR = os.path.join(HERE, "lib")
 ABI_SYMBOLS = [
     "svslam_create", "svslam_destroy", "svslam_last_error", "svslam_build_info",
     "svslam_pyramid_batch", "svslam_pyramid_decimate_batch", "svslam_set_source_size", "svslam_set_low_latency", "svslam_set_pose_only_xtol", "svslam_get_pose_only_xtol", "svslam_pyramid_read",
-    "svslam_pyramid_read_padded", "svslam_stereo_bm_batch", "svslam_stereo_bm_strip_rows", "svslam_dense_cloud_batch", "svslam_cloud_sor_batch", "svslam_cloud_voxel_grid", "svslam_debug_cloud_sor_climbs", "svslam_lk_batch", "svslam_gftt_batch", "svslam_gftt_eigmap", "svslam_triangulate_batch",
+    "svslam_pyramid_read_padded", "svslam_stereo_bm_batch", "svslam_stereo_bm_strip_rows", "svslam_dense_cloud_batch", "svslam_cloud_sor_batch", "svslam_cloud_voxel_grid", "svslam_debug_cloud_sor_climbs",
+    "svslam_colour_reserve", "svslam_pyramid_bgr_batch", "svslam_colour_read", "svslam_dense_cloud_bgr_batch", "svslam_lk_batch", "svslam_gftt_batch", "svslam_gftt_eigmap", "svslam_triangulate_batch",
     "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect", "svslam_pose_graph_batch", "svslam_loop_verify_batch", "svslam_brief_describe_batch", "svslam_brief_default_pattern",
     "svslam_loopdb_configure", "svslam_loopdb_append_batch", "svslam_loop_candidates_batch", "svslam_loopdb_count", "svslam_loopdb_read",
     "svslam_gdesc_configure", "svslam_gdesc_dim", "svslam_gdesc_describe_batch", "svslam_gdesc_mobilenet_v2",
@@ -43,6 +44,8 @@ CLOUD_FAMILIES = {"cloud_filter": 12}      # the outlier removal and the voxel g
 # 13 and 14, nothing renumbered; svslam_loop_candidates_batch (units = rows compared) appended after 15
 # svslam_gdesc_describe_batch (units = jobs) appended after 16
 LOOP_FAMILIES = {"pose_graph": 13, "loop_verify": 14, "brief": 15, "loop_candidates": 16, "global_desc": 17}
+# svslam_pyramid_bgr_batch's conversion kernel (units = images), appended after 17; a dictionary of its own: the dense program's, not the per-frame loop's
+COLOUR_FAMILIES = {"colour": 18}
 # the HIP kernel(s) behind each timing family at the batch operating point (what a rocprofv3 --kernel-trace --stats row is named)
 FAMILY_KERNELS = {"pyramid": ["k_pyr_fused"], "lk": ["k_lk"], "gftt": ["k_gftt_eig3", "k_gftt_select2"], "triangulate": ["k_triangulate"],
                   "pose_only": ["k_pose_only"], "local_ba": ["k_dmap_ba_gather", "k_ba_build", "k_local_ba_t", "k_dmap_ba_scatter"],
@@ -50,6 +53,7 @@ FAMILY_KERNELS = {"pyramid": ["k_pyr_fused"], "lk": ["k_lk"], "gftt": ["k_gftt_e
                   "cloud_filter": ["k_cf_keys", "k_cf_gather", "k_cf_knn", "k_vg_keys", "k_vg_heads", "k_vg_starts", "k_vg_reduce"],
                   "pose_graph": ["k_pose_graph"], "loop_verify": ["k_loop_verify"], "brief": ["k_brief_filter", "k_brief_describe"],
                   "loop_candidates": ["k_lc_candidates"],
+                  "colour": ["k_bgr_prepare"],
                   "global_desc": ["k_gd_prep", "k_gd_conv3", "k_gd_dw3", "k_gd_pw_mfma", "k_gd_pool"]}
 
 
@@ -411,7 +415,7 @@ class Context:
 
     def timing_get(self, family):
         ms, n, u = C.c_double(), C.c_longlong(), C.c_longlong()
-        fam = next(t[family] for t in (FAMILIES, KERNEL_FAMILIES, DENSE_FAMILIES, CLOUD_FAMILIES, LOOP_FAMILIES, DEBUG_FAMILIES) if family in t)
+        fam = next(t[family] for t in (FAMILIES, KERNEL_FAMILIES, DENSE_FAMILIES, CLOUD_FAMILIES, LOOP_FAMILIES, COLOUR_FAMILIES, DEBUG_FAMILIES) if family in t)
         self._chk(self.L.svslam_timing_get(self.h, fam, C.byref(ms), C.byref(n), C.byref(u)), "timing")
         return ms.value, n.value, u.value
 
@@ -503,6 +507,63 @@ class Context:
                                                   C.c_double(min_depth), cap, _p(xyz), _p(pix), _p(disp)), "dense_cloud_batch")
         return [(xyz[j.pt_ofs:j.pt_ofs + j.n_points].copy(), pix[j.pt_ofs:j.pt_ofs + j.n_points].copy(), disp[i].copy())
                 for i, j in enumerate(arr[:n])]
+
+    # ---- colour input of the dense program ---------------------------------
+    def colour_reserve(self, n):
+        """n colour planes [height, width, 3] (b, g, r) on the device (svslam_colour_reserve); 0 frees, a new count drops the contents"""
+        self._chk(self.L.svslam_colour_reserve(self.h, int(n)), "colour_reserve")
+
+    def pyramid_bgr(self, slots, planes, imgs, device=False, strides=None):
+        """packed BGR images -> pyramid slots (from the grey image, made on the device) and colour planes (svslam_pyramid_bgr_batch).
+        planes: a plane per image, -1 keeps no colour.  imgs: uint8 [H, W, 3], all of one shape: the context's, or one that
+        halves to it (then dst(x, y) = src(2x, 2y)).  device=True: imgs are (pointer, H, W) of images in device memory,
+        strides their bytes per row (default 3 W)."""
+        n = len(slots)
+        if len(planes) != n or len(imgs) != n:
+            raise ValueError("slots, planes and imgs differ in length")
+        sl = (C.c_int * max(n, 1))(*[int(v) for v in slots]); pl = (C.c_int * max(n, 1))(*[int(v) for v in planes])
+        keep = []
+        if device:
+            shapes = {(int(h), int(w)) for _, h, w in imgs}
+            ptrs = (C.c_void_p * max(n, 1))(*[C.c_void_p(int(p)) for p, _, _ in imgs])
+            st = [3 * int(w) for _, _, w in imgs] if strides is None else [int(v) for v in strides]
+        else:
+            # a view whose pixels are packed keeps its row stride; anything else is copied tight
+            keep = [im if isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.strides[1:] == (3, 1) and im.strides[0] >= 3 * im.shape[1]
+                    else np.ascontiguousarray(im, np.uint8) for im in imgs]
+            if any(im.ndim != 3 or im.shape[2] != 3 for im in keep):
+                raise ValueError("pyramid_bgr takes uint8 [H, W, 3] images")
+            shapes = {im.shape[:2] for im in keep}
+            ptrs = (C.c_void_p * max(n, 1))(*[im.ctypes.data for im in keep])
+            st = [im.strides[0] for im in keep]
+        if len(shapes) > 1:
+            raise ValueError("the images of one call have one shape")
+        sh, sw = shapes.pop() if shapes else (self.height, self.width)
+        self._chk(self.L.svslam_pyramid_bgr_batch(self.h, n, sl, pl, ptrs, (C.c_int * max(n, 1))(*st), int(sw), int(sh), 1 if device else 0), "pyramid_bgr_batch")
+
+    def colour_read(self, plane):
+        """test hook (svslam_colour_read): a colour plane, uint8 [height, width, 3]"""
+        out = np.zeros((self.height, self.width, 3), np.uint8)
+        self._chk(self.L.svslam_colour_read(self.h, int(plane), _p(out)), "colour_read")
+        return out
+
+    def dense_cloud_bgr(self, jobs, cam_l, ext_l, baseline, min_depth=1.0, max_pts_per_job=None, **params):
+        """dense_cloud with the colour of every point (svslam_dense_cloud_bgr_batch).  jobs: list of (slot_left, slot_right, plane,
+        T_cw[7] or None).  returns per job (xyz, pix, bgr uint8 [n, 3], disp); xyz, pix and disp are dense_cloud's."""
+        n = len(jobs)
+        cap = self.width * self.height if max_pts_per_job is None else int(max_pts_per_job)
+        arr = (DenseJob * max(n, 1))()
+        for i, (sl, sr, _, T) in enumerate(jobs):
+            arr[i] = DenseJob(int(sl), int(sr), i * cap, 0, (C.c_double * 7)(*(IDENT if T is None else _d(T))))
+        pl = (C.c_int * max(n, 1))(*[int(j[2]) for j in jobs])
+        xyz = np.zeros((max(n * cap, 1), 3), np.float32); pix = np.zeros(max(n * cap, 1), np.int32)
+        bgr = np.zeros((max(n * cap, 1), 3), np.uint8)
+        disp = np.zeros((n, self.height, self.width), np.int16)
+        prm = self._bm_params(**params)
+        self._chk(self.L.svslam_dense_cloud_bgr_batch(self.h, n, arr, _p(_d(cam_l)), _p(_d(ext_l)), C.c_double(baseline), C.byref(prm),
+                                                      C.c_double(min_depth), cap, pl, _p(xyz), _p(pix), _p(bgr), _p(disp)), "dense_cloud_bgr_batch")
+        return [(xyz[j.pt_ofs:j.pt_ofs + j.n_points].copy(), pix[j.pt_ofs:j.pt_ofs + j.n_points].copy(),
+                 bgr[j.pt_ofs:j.pt_ofs + j.n_points].copy(), disp[i].copy()) for i, j in enumerate(arr[:n])]
 
     # ---- cloud filters ---------------------------------------------------
     def cloud_sor(self, clouds, mean_k=50, stddev_mul=1.0):

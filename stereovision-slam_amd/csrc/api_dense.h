@@ -1,5 +1,6 @@
 // api_dense.h — included by svslam_hip.hip.  Entry points: svslam_stereo_bm_*, svslam_dense_cloud_batch, svslam_cloud_sor_batch,
-// svslam_cloud_voxel_grid, svslam_debug_cloud_sor_climbs.  Owns of svslam_ctx: bm, cf.
+// svslam_cloud_voxel_grid, svslam_debug_cloud_sor_climbs, svslam_colour_reserve, svslam_pyramid_bgr_batch, svslam_colour_read,
+// svslam_dense_cloud_bgr_batch.  Owns of svslam_ctx: bm, cf, col.
 
 extern "C" {
 
@@ -89,9 +90,10 @@ int svslam_stereo_bm_batch(svslam_ctx *c, int njobs, const svslam_bm_job *jobs, 
     return 0;
 }
 
-int svslam_dense_cloud_batch(svslam_ctx *c, int njobs, svslam_dense_job *jobs, const double cam_l[4], const double ext_l[7], double baseline,
-                             const svslam_bm_params *p, double min_depth, int max_pts_per_job, float *out_xyz, int *out_pix,
-                             int16_t *out_disp_or_null)
+// svslam_dense_cloud_batch, and with planes / out_bgr svslam_dense_cloud_bgr_batch: the same launches, then the colour gather
+static int dense_cloud_common(svslam_ctx *c, int njobs, svslam_dense_job *jobs, const double cam_l[4], const double ext_l[7], double baseline,
+                              const svslam_bm_params *p, double min_depth, int max_pts_per_job, float *out_xyz, int *out_pix,
+                              int16_t *out_disp_or_null, bool colour, const int *planes, uint8_t *out_bgr)
 {
     if (!c) return -1;
     BmParams P;
@@ -105,10 +107,20 @@ int svslam_dense_cloud_batch(svslam_ctx *c, int njobs, svslam_dense_job *jobs, c
         if (check_slot(c, jobs[i].slot_left) || check_slot(c, jobs[i].slot_right)) return -1;
         if (jobs[i].pt_ofs < 0) return fail(c, "dense_cloud: job %d: negative pt_ofs", i);
     }
+    if (colour) {
+        if (!planes || !out_bgr) return fail(c, "colour: null planes / out_bgr");
+        if (c->col.nplanes <= 0) return fail(c, "colour: no planes reserved (svslam_colour_reserve)");
+        for (int i = 0; i < njobs; ++i) {
+            if (planes[i] < 0 || planes[i] >= c->col.nplanes) return fail(c, "colour: job %d: plane %d out of range [0,%d)", i, planes[i], c->col.nplanes);
+            if (!c->col.written[(size_t)planes[i]]) return fail(c, "colour: job %d: plane %d has not been written since it was reserved", i, planes[i]);
+        }
+    }
     if (arena_busy(c)) return -1;
     const int w = c->geom.w[0], h = c->geom.h[0];
     const size_t N = (size_t)w * h;
     const int cap = (int)std::min<size_t>((size_t)max_pts_per_job, N);     // a job has at most w h survivors
+    const size_t bgr_per = ((size_t)3 * (size_t)(((cap + 3) / 4) * 4) + 15) & ~(size_t)15;      // k_colour_gather: 12 bytes per 4 points
+    if (colour && c->col.bgr.reserve(c, "colour", bgr_per * (size_t)c->lim.max_jobs, 0)) return -1;
     if (!c->bm.xyz) HIPCHK(c, hipMalloc(&c->bm.xyz, sizeof(float) * 3 * N * c->lim.max_jobs));
     if (!c->bm.pix) HIPCHK(c, hipMalloc(&c->bm.pix, sizeof(int) * N * c->lim.max_jobs));
     c->ar.reset();
@@ -117,6 +129,8 @@ int svslam_dense_cloud_batch(svslam_ctx *c, int njobs, svslam_dense_job *jobs, c
     const size_t oj = c->ar.take(sizeof(DenseJob) * njobs);
     for (int i = 0; i < njobs; ++i) { hp<BmJob>(c, obm)[i].slot_left = jobs[i].slot_left; hp<BmJob>(c, obm)[i].slot_right = jobs[i].slot_right; }
     memcpy(hp<void>(c, oj), jobs, sizeof(DenseJob) * njobs);
+    const size_t opl = c->ar.take(sizeof(int) * njobs);
+    if (colour) memcpy(hp<void>(c, opl), planes, sizeof(int) * njobs);
     if (h2d(c, 0, c->ar.off)) return -1;
     DenseCam cam;
     cam.fx = cam_l[0]; cam.fy = cam_l[1]; cam.cx = cam_l[2]; cam.cy = cam_l[3];
@@ -126,6 +140,11 @@ int svslam_dense_cloud_batch(svslam_ctx *c, int njobs, svslam_dense_job *jobs, c
     tm_begin(c, FAM_BM, njobs);
     const int rc = launch_stereo_bm(c, njobs, dp<BmJob>(c, obm), P);
     if (!rc) hipLaunchKernelGGL(k_dense_cloud, dim3(njobs), dim3(DC_THREADS), 0, c->stream, dp<DenseJob>(c, oj), c->bm.disp, w, h, cam, cap, c->bm.xyz, c->bm.pix);
+    static_assert(sizeof(DenseJob) % sizeof(int) == 0 && offsetof(DenseJob, n_points) == 3 * sizeof(int), "n_points as k_colour_gather reads it");
+    if (!rc && colour)
+        hipLaunchKernelGGL(k_colour_gather, dim3(cdiv(cdiv(cap, 4), COL_THREADS), njobs), dim3(COL_THREADS), 0, c->stream, dp<int>(c, oj) + 3,
+                           (int)(sizeof(DenseJob) / sizeof(int)), dp<int>(c, opl), (const int *)c->bm.pix, cap, (const uint8_t *)c->col.planes.d, 3 * N,
+                           (uint8_t *)c->col.bgr.d, bgr_per);
     tm_end(c);
     if (rc) return -1;
     HIPCHK(c, hipGetLastError());
@@ -139,8 +158,120 @@ int svslam_dense_cloud_batch(svslam_ctx *c, int njobs, svslam_dense_job *jobs, c
         if (!n) continue;
         HIPCHK(c, hipMemcpy(out_xyz + 3 * (size_t)jobs[i].pt_ofs, c->bm.xyz + 3 * (size_t)i * cap, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
         HIPCHK(c, hipMemcpy(out_pix + (size_t)jobs[i].pt_ofs, c->bm.pix + (size_t)i * cap, sizeof(int) * n, hipMemcpyDeviceToHost));
+        if (colour) HIPCHK(c, hipMemcpy(out_bgr + 3 * (size_t)jobs[i].pt_ofs, c->col.bgr.d + (size_t)i * bgr_per, 3 * n, hipMemcpyDeviceToHost));
     }
     if (out_disp_or_null) HIPCHK(c, hipMemcpy(out_disp_or_null, c->bm.disp, sizeof(int16_t) * N * njobs, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int svslam_dense_cloud_batch(svslam_ctx *c, int njobs, svslam_dense_job *jobs, const double cam_l[4], const double ext_l[7], double baseline,
+                             const svslam_bm_params *p, double min_depth, int max_pts_per_job, float *out_xyz, int *out_pix,
+                             int16_t *out_disp_or_null)
+{
+    return dense_cloud_common(c, njobs, jobs, cam_l, ext_l, baseline, p, min_depth, max_pts_per_job, out_xyz, out_pix, out_disp_or_null, false, nullptr, nullptr);
+}
+
+// ------------------------------------------------------------------ colour input (src/dense_reconstruction.cpp:104-171)
+int svslam_dense_cloud_bgr_batch(svslam_ctx *c, int njobs, svslam_dense_job *jobs, const double cam_l[4], const double ext_l[7], double baseline,
+                                 const svslam_bm_params *p, double min_depth, int max_pts_per_job, const int *planes, float *out_xyz,
+                                 int *out_pix, uint8_t *out_bgr, int16_t *out_disp_or_null)
+{
+    return dense_cloud_common(c, njobs, jobs, cam_l, ext_l, baseline, p, min_depth, max_pts_per_job, out_xyz, out_pix, out_disp_or_null, true, planes, out_bgr);
+}
+
+int svslam_colour_reserve(svslam_ctx *c, int nplanes)
+{
+    if (!c) return -1;
+    if (nplanes < 0 || nplanes > 1 << 16) return fail(c, "colour: %d planes out of [0, 65536]", nplanes);
+    if (nplanes == c->col.nplanes) return 0;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->col.planes.release();
+    c->col.nplanes = 0;
+    c->col.written.clear();
+    if (nplanes == 0) return 0;
+    if (c->col.planes.reserve(c, "colour", (size_t)3 * c->geom.w[0] * c->geom.h[0] * (size_t)nplanes, 0)) return -1;
+    c->col.nplanes = nplanes;
+    c->col.written.assign((size_t)nplanes, 0);
+    return 0;
+}
+
+int svslam_pyramid_bgr_batch(svslam_ctx *c, int n, const int *slots, const int *planes, const void *const *imgs, const int *strides,
+                             int src_w, int src_h, int src_is_device)
+{
+    if (!c) return -1;
+    if (n <= 0) return 0;
+    if (!slots || !planes || !imgs || !strides) return fail(c, "colour: null argument");
+    if (n > c->lim.max_jobs) return fail(c, "colour: %d images > max_jobs %d", n, c->lim.max_jobs);
+    const int w = c->geom.w[0], h = c->geom.h[0];
+    bool decimate = false;
+    if (src_w != w || src_h != h) {
+        // svslam_pyramid_decimate_batch's rule, cvRound(src * 0.5): round half to even
+        const int dw = src_w > 0 ? (int)std::nearbyint(src_w * 0.5) : -1, dh = src_h > 0 ? (int)std::nearbyint(src_h * 0.5) : -1;
+        if (dw != w || dh != h) return fail(c, "colour: source %dx%d is not the context's %dx%d and does not halve to it", src_w, src_h, w, h);
+        decimate = true;
+    }
+    if ((long long)3 * src_w > INT32_MAX / 2) return fail(c, "colour: source width %d too large", src_w);
+    for (int i = 0; i < n; ++i) {
+        if (!imgs[i]) return fail(c, "colour: image %d is null", i);
+        if (check_slot(c, slots[i])) return -1;
+        if (strides[i] > INT32_MAX / 2) return fail(c, "colour: image %d: stride %d too large", i, strides[i]);
+        if (strides[i] < 3 * src_w) return fail(c, "colour: image %d: stride %d < 3 * %d", i, strides[i], src_w);
+        if (planes[i] < -1 || planes[i] >= std::max(c->col.nplanes, 0)) {
+            if (planes[i] >= 0 && c->col.nplanes <= 0) return fail(c, "colour: no planes reserved (svslam_colour_reserve)");
+            return fail(c, "colour: image %d: plane %d out of range [-1,%d)", i, planes[i], c->col.nplanes);
+        }
+        for (int k = 0; k < i; ++k) if (planes[i] >= 0 && planes[k] == planes[i]) return fail(c, "colour: plane %d named twice (images %d and %d)", planes[i], k, i);
+    }
+    if (arena_busy(c)) return -1;
+    const size_t grey_per = ((size_t)w * h + 255) & ~(size_t)255;
+    if (c->col.grey.reserve(c, "colour", grey_per * (size_t)c->lim.max_jobs + 256, 0)) return -1;
+    c->ar.reset();
+    const size_t ob = c->ar.take(sizeof(BgrJob) * n), opj = c->ar.take(sizeof(PyrJob) * n);
+    BgrJob *bj = hp<BgrJob>(c, ob);
+    PyrJob *pj = hp<PyrJob>(c, opj);
+    if (!src_is_device) {
+        // only the rows the kernel reads are staged: every row, or the even ones
+        const int rows = decimate ? h : src_h, step = decimate ? 2 : 1;
+        const size_t rb = (size_t)3 * src_w, per = (rb * (size_t)rows + 255) & ~(size_t)255;
+        if (c->img.reserve(c, "colour", per * (size_t)n, 0, 0, true)) return -1;
+        for (int i = 0; i < n; ++i) {
+            const uint8_t *s = static_cast<const uint8_t *>(imgs[i]);
+            uint8_t *d = c->img.pin + per * i;
+            for (int y = 0; y < rows; ++y) memcpy(d + (size_t)y * rb, s + (size_t)(y * step) * (size_t)strides[i], rb);
+            bj[i].src = c->img.d + per * i;
+            bj[i].stride = (int)rb;
+        }
+        HIPCHK(c, hipMemcpyAsync(c->img.d, c->img.pin, per * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    } else {
+        for (int i = 0; i < n; ++i) { bj[i].src = static_cast<const uint8_t *>(imgs[i]); bj[i].stride = decimate ? 2 * strides[i] : strides[i]; }
+    }
+    for (int i = 0; i < n; ++i) {
+        bj[i].plane = planes[i];
+        pj[i].src = c->col.grey.d + grey_per * i; pj[i].src_stride = w; pj[i].slot = slots[i];
+    }
+    if (h2d(c, 0, c->ar.off)) return -1;
+    const int chunks = cdiv(w, COL_PX);
+    const dim3 grid(cdiv(h * chunks, COL_THREADS), n);
+    tm_begin(c, FAM_COL, n);
+    if (decimate) hipLaunchKernelGGL(k_bgr_prepare<true>, grid, dim3(COL_THREADS), 0, c->stream, dp<BgrJob>(c, ob), w, h, src_w, chunks, (uint8_t *)c->col.grey.d, grey_per, (uint8_t *)c->col.planes.d);
+    else hipLaunchKernelGGL(k_bgr_prepare<false>, grid, dim3(COL_THREADS), 0, c->stream, dp<BgrJob>(c, ob), w, h, src_w, chunks, (uint8_t *)c->col.grey.d, grey_per, (uint8_t *)c->col.planes.d);
+    tm_end(c);
+    HIPCHK(c, hipGetLastError());
+    if (launch_pyramid(c, dp<PyrJob>(c, opj), n, false, w, h)) return -1;
+    if (d2h_sync(c, 0, 0)) return -1;
+    for (int i = 0; i < n; ++i) if (planes[i] >= 0) c->col.written[(size_t)planes[i]] = 1;
+    return 0;
+}
+
+int svslam_colour_read(svslam_ctx *c, int plane, uint8_t *out)
+{
+    if (!c) return -1;
+    if (!out) return fail(c, "colour: null output");
+    if (c->col.nplanes <= 0) return fail(c, "colour: no planes reserved (svslam_colour_reserve)");
+    if (plane < 0 || plane >= c->col.nplanes) return fail(c, "colour: plane %d out of range [0,%d)", plane, c->col.nplanes);
+    const size_t bytes = (size_t)3 * c->geom.w[0] * c->geom.h[0];
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, c->col.planes.d + bytes * (size_t)plane, bytes, hipMemcpyDeviceToHost));
     return 0;
 }
 

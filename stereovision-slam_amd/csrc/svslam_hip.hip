@@ -53,6 +53,7 @@ typedef enum { ncclDouble = 8 } ncclDataType_t;
 #include "k_brief.h"
 #include "k_loop_candidates.h"
 #include "k_global_desc.h"
+#include "k_colour.h"
 
 #define SVSLAM_DMAP_CHUNK 512     /* keyframe jobs per svslam_dmap_keyframe_batch call the staging arena is sized for */
 #define SVSLAM_DMAP_EVICT_PER_JOB 512   /* evicted-landmark records per job of a call (shared by the call's jobs; the surplus waits) */
@@ -70,6 +71,7 @@ enum { FAM_PYR = 0, FAM_LK, FAM_GFTT, FAM_TRI, FAM_POSE, FAM_BA,
        FAM_BRIEF,      // 15: "brief", svslam_brief_describe_batch (units = points); appended, nothing moved
        FAM_LC,         // 16: "loop_candidates", svslam_loop_candidates_batch (units = rows compared); appended, nothing moved
        FAM_GD,         // 17: "global_desc", svslam_gdesc_describe_batch (units = jobs); appended, nothing moved
+       FAM_COL,        // 18: "colour", k_bgr_prepare of svslam_pyramid_bgr_batch (units = images); appended, nothing moved
        FAM_COUNT };
 
 struct Timing {
@@ -142,6 +144,9 @@ struct svslam_ctx {
     // global descriptor (svslam_gdesc_*): the configured network, its parameters and resize tables on the device, the workspace of a
     // chunk of jobs (ws) and a call's slots / vectors (io, with the host mirror of the vectors), allocated inside the call on demand and kept
     struct { GdNet N; float *d_prm = nullptr; int *d_tab = nullptr; DevBuf ws, io; } gd;
+    // colour input of the dense program (svslam_colour_reserve / svslam_pyramid_bgr_batch / svslam_dense_cloud_bgr_batch): the
+    // working-resolution BGR planes, which of them an upload has written, the staged grey images of a call, a call's point colours
+    struct { DevBuf planes, grey, bgr; int nplanes = 0; std::vector<uint8_t> written; } col;
     // BA scratch
     BaWork bw;
     int bw_jobs = 0;          // problems per call the BA scratch holds

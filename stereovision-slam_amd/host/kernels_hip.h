@@ -71,6 +71,13 @@ public:
     int dense_cloud(int n, svslam_dense_job *jobs, const double *cam_l, const double *ext_l, double baseline, const svslam_bm_params *p,
                     double min_depth, int max_pts_per_job, float *out_xyz, int *out_pix, int16_t *out_disp)
     { return svslam_dense_cloud_batch(ctx_, n, jobs, cam_l, ext_l, baseline, p, min_depth, max_pts_per_job, out_xyz, out_pix, out_disp); }
+    // colour input of the dense program (:104-171): BGR images -> slots and colour planes, the cloud with its colours
+    int colour_reserve(int nplanes) { return svslam_colour_reserve(ctx_, nplanes); }
+    int pyramid_bgr(int n, const int *slots, const int *planes, const void *const *imgs, const int *strides, int src_w, int src_h, int is_device)
+    { return svslam_pyramid_bgr_batch(ctx_, n, slots, planes, imgs, strides, src_w, src_h, is_device); }
+    int dense_cloud_bgr(int n, svslam_dense_job *jobs, const double *cam_l, const double *ext_l, double baseline, const svslam_bm_params *p,
+                        double min_depth, int max_pts_per_job, const int *planes, float *out_xyz, int *out_pix, uint8_t *out_bgr, int16_t *out_disp)
+    { return svslam_dense_cloud_bgr_batch(ctx_, n, jobs, cam_l, ext_l, baseline, p, min_depth, max_pts_per_job, planes, out_xyz, out_pix, out_bgr, out_disp); }
     // the cloud filters of :175-209 (pcl::StatisticalOutlierRemoval on nseg clouds at once, pcl::VoxelGrid)
     int cloud_sor(int nseg, const int64_t *seg_ofs, const float *xyz, int mean_k, double stddev_mul, uint8_t *out_keep, double *out_threshold)
     { return svslam_cloud_sor_batch(ctx_, nseg, seg_ofs, xyz, mean_k, stddev_mul, out_keep, nullptr, out_threshold); }

@@ -17,7 +17,7 @@
 //                                                           run_dense_reconstruction: keyframes.txt -> dense_map.pcd)
 //
 // Differences, all forced by the missing third-party libraries: cv::Mat becomes facade::Image (u8, one
-// channel), Sophus::SE3d becomes svs::SE3 (same 7 doubles), Frame::Ptr / Camera::Ptr stay shared_ptrs.
+// channel, or three in b, g, r order for the dense program's colour input), Sophus::SE3d becomes svs::SE3 (same 7 doubles), Frame::Ptr / Camera::Ptr stay shared_ptrs.
 // The loop-closure and viewer objects of the reference are callbacks here (SetLoopClosure / SetViewer):
 // they receive exactly what src/frontend.cpp:631-640 hands them, the new keyframe.  The backend
 // "thread" is the pipeline's deterministic schedule: Backend::UpdateMap() from outside
@@ -47,16 +47,20 @@ namespace facade {
 
 struct SLAMException : std::runtime_error { using std::runtime_error::runtime_error; };   // slamexception.h
 
-struct Image {                       // stand-in for cv::Mat CV_8UC1
+struct Image {                       // stand-in for cv::Mat CV_8UC1 (channels 1) / CV_8UC3 in b, g, r order (channels 3)
     int cols = 0, rows = 0;
-    std::vector<uint8_t> data;
+    int channels = 1;
+    std::vector<uint8_t> data;       // tight rows of cols * channels bytes
     bool empty() const { return data.empty(); }
 };
 
 // ---- image files: 8-bit PNG (grey, grey+alpha, RGB, RGBA; non-interlaced) through zlib, and binary PGM.
-// cv::imread(path, IMREAD_GRAYSCALE): colour becomes grey with OpenCV's fixed-point BT.601 weights.
+// cv::imread(path, IMREAD_GRAYSCALE): colour becomes grey by SVSLAM_GREY_FROM_RGB (include/svslam.h; the device conversion of
+// the dense program's colour input uses the same definition).  cv::imread(path, IMREAD_COLOR): three channels b, g, r; a grey
+// file is replicated into them, alpha is dropped.
+enum ImreadModes { IMREAD_GRAYSCALE = 0, IMREAD_COLOR = 1 };
 inline uint32_t be32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
-inline bool read_png(const std::vector<uint8_t> &f, Image &img)
+inline bool read_png(const std::vector<uint8_t> &f, Image &img, bool colour = false)
 {
     static const uint8_t sig[8] = { 0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a };
     if (f.size() < 33 || std::memcmp(f.data(), sig, 8) != 0) return false;
@@ -90,7 +94,8 @@ inline bool read_png(const std::vector<uint8_t> &f, Image &img)
     uLongf rawlen = (uLongf)raw.size();
     if (uncompress(raw.data(), &rawlen, z.data(), (uLong)z.size()) != Z_OK || rawlen != raw.size()) return false;
     std::vector<uint8_t> cur(stride), prev(stride, 0);
-    img.cols = (int)w; img.rows = (int)h; img.data.assign((size_t)w * h, 0);
+    const size_t oc = colour ? 3 : 1;
+    img.cols = (int)w; img.rows = (int)h; img.channels = (int)oc; img.data.assign((size_t)w * h * oc, 0);
     for (uint32_t y = 0; y < h; ++y) {
         const uint8_t *r = &raw[(stride + 1) * y];
         const int ft = r[0];
@@ -104,17 +109,22 @@ inline bool read_png(const std::vector<uint8_t> &f, Image &img)
             else if (ft != 0) return false;
             cur[i] = (uint8_t)v;
         }
-        uint8_t *o = &img.data[(size_t)y * w];
-        if (ch <= 2) for (uint32_t x = 0; x < w; ++x) o[x] = cur[(size_t)x * ch];
-        else for (uint32_t x = 0; x < w; ++x) {       // cv::cvtColor RGB2GRAY: (R*4899 + G*9617 + B*1868 + 8192) >> 14
+        uint8_t *o = &img.data[(size_t)y * w * oc];
+        if (colour) for (uint32_t x = 0; x < w; ++x) {
             const uint8_t *q = &cur[(size_t)x * ch];
-            o[x] = (uint8_t)((q[0] * 4899 + q[1] * 9617 + q[2] * 1868 + 8192) >> 14);
+            if (ch <= 2) o[3 * x] = o[3 * x + 1] = o[3 * x + 2] = q[0];
+            else { o[3 * x] = q[2]; o[3 * x + 1] = q[1]; o[3 * x + 2] = q[0]; }       // the file holds r, g, b
+        }
+        else if (ch <= 2) for (uint32_t x = 0; x < w; ++x) o[x] = cur[(size_t)x * ch];
+        else for (uint32_t x = 0; x < w; ++x) {       // cv::cvtColor RGB2GRAY
+            const uint8_t *q = &cur[(size_t)x * ch];
+            o[x] = (uint8_t)SVSLAM_GREY_FROM_RGB(q[0], q[1], q[2]);
         }
         prev.swap(cur);
     }
     return true;
 }
-inline bool read_pgm(const std::vector<uint8_t> &f, Image &img)
+inline bool read_pgm(const std::vector<uint8_t> &f, Image &img, bool colour = false)
 {
     if (f.size() < 7 || f[0] != 'P' || f[1] != '5') return false;
     size_t p = 2;
@@ -130,18 +140,24 @@ inline bool read_pgm(const std::vector<uint8_t> &f, Image &img)
     ++p;                                         // the single whitespace after maxval
     if (n < 3 || vals[2] != 255 || vals[0] <= 0 || vals[1] <= 0 || vals[0] > 16384 || vals[1] > 16384 ||
         p + (size_t)vals[0] * vals[1] > f.size()) return false;
-    img.cols = vals[0]; img.rows = vals[1];
-    img.data.assign(f.begin() + (long)p, f.begin() + (long)p + (long)vals[0] * vals[1]);
+    img.cols = vals[0]; img.rows = vals[1]; img.channels = colour ? 3 : 1;
+    if (!colour) img.data.assign(f.begin() + (long)p, f.begin() + (long)p + (long)vals[0] * vals[1]);
+    else {
+        const size_t n = (size_t)vals[0] * (size_t)vals[1];
+        img.data.resize(3 * n);
+        for (size_t i = 0; i < n; ++i) img.data[3 * i] = img.data[3 * i + 1] = img.data[3 * i + 2] = f[p + i];
+    }
     return true;
 }
-inline Image imread(const std::string &path)     // empty image when the file is missing or not understood, like cv::imread
+inline Image imread(const std::string &path, int flags = IMREAD_GRAYSCALE)     // empty image when the file is missing or not understood, like cv::imread
 {
+    const bool colour = flags == IMREAD_COLOR;
     Image img;
     std::ifstream in(path, std::ios::binary);
     if (!in) return img;
     std::vector<uint8_t> f((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
     try {
-        if (!read_png(f, img) && !read_pgm(f, img)) img = Image();
+        if (!read_png(f, img, colour) && !read_pgm(f, img, colour)) img = Image();
     } catch (const std::exception &) { img = Image(); }        // bad_alloc / length_error on a corrupt header
     return img;
 }
@@ -558,8 +574,9 @@ private:
 class Dataset {
 public:
     typedef std::shared_ptr<Dataset> Ptr;
-    explicit Dataset(const std::string &dataset_path, int left_cam_index = 0, int right_cam_index = 1)
-        : dataset_path_(dataset_path), left_cam_index_(left_cam_index), right_cam_index_(right_cam_index) {}
+    // color_input: read with IMREAD_COLOR (src/dataset.cpp reads is_color_input from the config); only the dense program asks for it
+    explicit Dataset(const std::string &dataset_path, int left_cam_index = 0, int right_cam_index = 1, bool color_input = false)
+        : dataset_path_(dataset_path), left_cam_index_(left_cam_index), right_cam_index_(right_cam_index), color_input_(color_input) {}
 
     bool initialize()                             // :24-86
     {
@@ -610,12 +627,14 @@ private:
     {
         std::ostringstream base;
         base << dataset_path_ << "/image_" << cam << "/" << std::setw(6) << std::setfill('0') << id;
-        Image img = imread(base.str() + ".png");
-        if (img.empty()) img = imread(base.str() + ".pgm");
+        const int flags = color_input_ ? IMREAD_COLOR : IMREAD_GRAYSCALE;
+        Image img = imread(base.str() + ".png", flags);
+        if (img.empty()) img = imread(base.str() + ".pgm", flags);
         return img;
     }
     std::string dataset_path_;
     int left_cam_index_, right_cam_index_;
+    bool color_input_ = false;
     std::vector<Camera::Ptr> cameras_;
     int current_image_index_ = 0;
 };
@@ -728,8 +747,12 @@ private:
 // Reads the dense config (slam_output_dir = the keyframes.txt VisualOdometry::saveSLAMOutputInFile wrote, left_cam_index,
 // right_cam_index, output_dir), runs cv::StereoBM(128, 15) and the back-projection of every keyframe on the device
 // (svslam_dense_cloud_batch, several keyframes per call) and writes output_dir/dense_map.pcd.
-// Differences from the reference, all stated in DESIGN 9: the image reader is GREYSCALE (facade::imread), so r = g = b = the
-// grey value of the left pixel; PCL's StatisticalOutlierRemoval (k = 50, once per keyframe cloud and once on the merge) and the
+// Colour: with `is_color_input: 1` in the dense config — what every dense config of the reference says — the images
+// are read IMREAD_COLOR, the grey images of the matcher are made on the device (svslam_pyramid_bgr_batch), the left image stays
+// there as a colour plane and every point comes back with its b, g, r (svslam_dense_cloud_bgr_batch); the colours pass through the
+// keep masks, the merge, both filters and the writer.  With 0 (this facade's default) the reader is greyscale and r = g = b = the
+// grey value of the left pixel.
+// Differences from the reference, all stated in DESIGN 9: PCL's StatisticalOutlierRemoval (k = 50, once per keyframe cloud and once on the merge) and the
 // 2 cm VoxelGrid (:175-209) run only with `cloud_filters: 1` in the dense config (svslam_cloud_sor_batch, svslam_cloud_voxel_grid;
 // their contract is tests/ref_cloud_filters.py) — the default 0 writes the unfiltered merge of the keyframe clouds in keyframe
 // order, as before the filters existed; the file goes to output_dir itself, not into a
@@ -795,12 +818,13 @@ public:
             if (!ok) break;
             keyframes_.push_back(DenseKeyframe{ image_id, se3_from_float_rows(m) });
         }
-        dataset_.reset(new Dataset(data_sequence_path_, left_cam_index_, right_cam_index_));
+        color_input_ = (int)config_.Num("is_color_input", 0) != 0;
+        dataset_.reset(new Dataset(data_sequence_path_, left_cam_index_, right_cam_index_, color_input_));
         if (!dataset_->initialize()) throw SLAMException("Cannot initialize object to read dataset.");
         params_.num_disparities = num_disparities_; params_.block_size = blockSize_;
         params_.pre_filter_cap = 31; params_.texture_threshold = 10; params_.uniqueness_ratio = 15; params_.reserved = 0;
         cloud_filters_ = (int)config_.Num("cloud_filters", 0) != 0;
-        xyz_.clear(); grey_.clear();
+        xyz_.clear(); bgr_.clear();
     }
 
     void DenseReconstruct()                       // :92-238
@@ -814,9 +838,11 @@ public:
         double cam[4];
         cl->k4(cam);
         const int B = 8;                           // keyframes per device call
-        xyz_.clear(); grey_.clear();
+        xyz_.clear(); bgr_.clear();
         std::vector<float> xyz;
         std::vector<int> pix;
+        std::vector<uint8_t> bgr;                  // b, g, r of every point of the call, indexed like xyz
+        const int ch = color_input_ ? 3 : 1;
         for (size_t k0 = 0; k0 < keyframes_.size(); k0 += (size_t)B) {
             const int nb = (int)std::min<size_t>((size_t)B, keyframes_.size() - k0);
             std::vector<Frame::Ptr> frames;
@@ -826,24 +852,43 @@ public:
                 if (!kernels_) create(f->left_img_.cols, f->left_img_.rows);
                 if (f->left_img_.cols != src_w_ || f->left_img_.rows != src_h_ || f->right_img_.cols != src_w_ || f->right_img_.rows != src_h_)
                     throw SLAMException("frame size changed");
+                if (f->left_img_.channels != ch || f->right_img_.channels != ch) throw SLAMException("frame channels changed");
                 frames.push_back(f);
             }
-            std::vector<int> slots; std::vector<const void *> imgs; std::vector<int> strides;
+            std::vector<int> slots, planes, job_planes; std::vector<const void *> imgs; std::vector<int> strides;
             std::vector<svslam_dense_job> jobs((size_t)nb);
             const int cap = w_ * h_;
             for (int i = 0; i < nb; ++i) {
                 slots.push_back(2 * i); slots.push_back(2 * i + 1);
                 imgs.push_back(frames[(size_t)i]->left_img_.data.data()); imgs.push_back(frames[(size_t)i]->right_img_.data.data());
-                strides.push_back(src_w_); strides.push_back(src_w_);
+                strides.push_back(ch * src_w_); strides.push_back(ch * src_w_);
+                planes.push_back(i); planes.push_back(-1); job_planes.push_back(i);          // the left image keeps its colours
                 svslam_dense_job &j = jobs[(size_t)i];
                 j.slot_left = 2 * i; j.slot_right = 2 * i + 1; j.pt_ofs = i * cap; j.n_points = 0;
                 std::memcpy(j.T_cw, keyframes_[k0 + (size_t)i].T_cw.v, sizeof(j.T_cw));
             }
-            if (kernels_->pyramid_decimate(2 * nb, slots.data(), imgs.data(), strides.data(), src_w_, src_h_, 0) != 0)
-                throw SLAMException(std::string("DenseReconstruction: ") + kernels_->last_error());
-            xyz.resize(3 * (size_t)cap * (size_t)nb); pix.resize((size_t)cap * (size_t)nb);
-            if (kernels_->dense_cloud(nb, jobs.data(), cam, cl->pose.v, baseline, &params_, 1.0, cap, xyz.data(), pix.data(), nullptr) != 0)
-                throw SLAMException(std::string("DenseReconstruction: ") + kernels_->last_error());
+            xyz.resize(3 * (size_t)cap * (size_t)nb); pix.resize((size_t)cap * (size_t)nb); bgr.resize(3 * (size_t)cap * (size_t)nb);
+            int rc;
+            if (color_input_) {
+                rc = kernels_->pyramid_bgr(2 * nb, slots.data(), planes.data(), imgs.data(), strides.data(), src_w_, src_h_, 0);
+                if (rc == 0)
+                    rc = kernels_->dense_cloud_bgr(nb, jobs.data(), cam, cl->pose.v, baseline, &params_, 1.0, cap, job_planes.data(), xyz.data(), pix.data(),
+                                                   bgr.data(), nullptr);
+            } else {
+                rc = kernels_->pyramid_decimate(2 * nb, slots.data(), imgs.data(), strides.data(), src_w_, src_h_, 0);
+                if (rc == 0) rc = kernels_->dense_cloud(nb, jobs.data(), cam, cl->pose.v, baseline, &params_, 1.0, cap, xyz.data(), pix.data(), nullptr);
+                // grey input: b = g = r = the left pixel, dst(x, y) = src(2x, 2y) (src/dataset.cpp:162-165)
+                for (int i = 0; rc == 0 && i < nb; ++i) {
+                    const svslam_dense_job &j = jobs[(size_t)i];
+                    const Image &src = frames[(size_t)i]->left_img_;
+                    for (int q = 0; q < j.n_points; ++q) {
+                        const size_t o = (size_t)j.pt_ofs + (size_t)q;
+                        const int y = pix[o] / w_, x = pix[o] - y * w_;
+                        bgr[3 * o] = bgr[3 * o + 1] = bgr[3 * o + 2] = src.data[(size_t)(2 * y) * (size_t)src_w_ + (size_t)(2 * x)];
+                    }
+                }
+            }
+            if (rc != 0) throw SLAMException(std::string("DenseReconstruction: ") + kernels_->last_error());
             // statistical_filter.filter(*tmp) of every keyframe cloud (:179-184): the call's keyframes are the segments of one batch
             std::vector<uint8_t> keep;
             if (cloud_filters_) {
@@ -862,27 +907,26 @@ public:
             size_t kpos = 0;
             for (int i = 0; i < nb; ++i) {
                 const svslam_dense_job &j = jobs[(size_t)i];
-                const Image &src = frames[(size_t)i]->left_img_;
                 for (int p = 0; p < j.n_points; ++p, ++kpos) {
                     if (cloud_filters_ && !keep[kpos]) continue;
                     const size_t o = (size_t)j.pt_ofs + (size_t)p;
                     xyz_.insert(xyz_.end(), xyz.begin() + 3 * (long)o, xyz.begin() + 3 * (long)o + 3);
-                    const int y = pix[o] / w_, x = pix[o] - y * w_;
-                    grey_.push_back(src.data[(size_t)(2 * y) * (size_t)src_w_ + (size_t)(2 * x)]);     // dst(x, y) = src(2x, 2y) (src/dataset.cpp:162-165)
+                    bgr_.insert(bgr_.end(), bgr.begin() + 3 * (long)o, bgr.begin() + 3 * (long)o + 3);
                 }
             }
         }
-        if (cloud_filters_ && !grey_.empty()) FilterMergedCloud();
+        if (cloud_filters_ && !bgr_.empty()) FilterMergedCloud();
         const std::string output_dir = config_.Str("output_dir", ".");
         map_file_ = output_dir + "/dense_map.pcd";
         if (!SavePCDFileBinary(map_file_)) throw SLAMException("DenseReconstruction: cannot write " + map_file_);
     }
 
-    // :190-209 — the outlier removal once more on the merged cloud, then the 2 cm voxel grid.  grey goes through the grid as
+    // :190-209 — the outlier removal once more on the merged cloud, then the 2 cm voxel grid with the points' colours (the grid
+    // takes three bytes per point in any order and averages each: b, g, r go in and come out).  Grey input goes through as
     // r = g = b; the three sums of a voxel are the same sum, so the centroid's colour is grey again.
     void FilterMergedCloud()
     {
-        const int64_t n = (int64_t)grey_.size();
+        const int64_t n = (int64_t)(bgr_.size() / 3);
         const int64_t seg_ofs[2] = { 0, n };
         std::vector<uint8_t> keep((size_t)n);
         double thr = 0;
@@ -893,7 +937,7 @@ public:
         for (size_t i = 0; i < (size_t)n; ++i) {
             if (!keep[i]) continue;
             fx.insert(fx.end(), xyz_.begin() + 3 * (long)i, xyz_.begin() + 3 * (long)i + 3);
-            frgb.insert(frgb.end(), 3, grey_[i]);
+            frgb.insert(frgb.end(), bgr_.begin() + 3 * (long)i, bgr_.begin() + 3 * (long)i + 3);
         }
         const int64_t nf = (int64_t)(frgb.size() / 3);
         std::vector<float> ox(3 * (size_t)nf + 3);
@@ -905,8 +949,7 @@ public:
             throw SLAMException(std::string("DenseReconstruction: ") + kernels_->last_error());
         if (overflowed) std::fprintf(stderr, "[pcl::VoxelGrid::applyFilter] Leaf size is too small for the input dataset. Integer indices would overflow.\n");
         xyz_.assign(ox.begin(), ox.begin() + 3 * (long)m);
-        grey_.resize((size_t)m);
-        for (size_t i = 0; i < (size_t)m; ++i) grey_[i] = orgb[3 * i];
+        bgr_.assign(orgb.begin(), orgb.begin() + 3 * (long)m);
     }
 
     // pcl::io::savePCDFileBinary of a PointXYZRGB cloud: PCD v0.7, x y z rgb, the colour packed r << 16 | g << 8 | b into the
@@ -915,12 +958,12 @@ public:
     {
         std::ofstream o(path, std::ios::binary);
         if (!o) return false;
-        const size_t n = grey_.size();
+        const size_t n = bgr_.size() / 3;
         o << "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\nTYPE F F F F\nCOUNT 1 1 1 1\nWIDTH " << n
           << "\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS " << n << "\nDATA binary\n";
         std::vector<char> rec(16 * n);
         for (size_t i = 0; i < n; ++i) {
-            const uint32_t g = grey_[i], rgb = (g << 16) | (g << 8) | g;
+            const uint32_t rgb = ((uint32_t)bgr_[3 * i + 2] << 16) | ((uint32_t)bgr_[3 * i + 1] << 8) | bgr_[3 * i];
             std::memcpy(&rec[16 * i], &xyz_[3 * i], 12);
             std::memcpy(&rec[16 * i + 12], &rgb, 4);
         }
@@ -929,7 +972,7 @@ public:
     }
 
     const std::vector<DenseKeyframe> &Keyframes() const { return keyframes_; }
-    size_t NumPoints() const { return grey_.size(); }
+    size_t NumPoints() const { return bgr_.size() / 3; }
     const std::string &MapFile() const { return map_file_; }
     Dataset::Ptr dataset() { return dataset_; }
     K *kernels() { return kernels_.get(); }
@@ -944,19 +987,22 @@ private:
         lim.device = (int)config_.Num("device", 0); lim.width = w_; lim.height = h_; lim.max_slots = 16; lim.max_jobs = 16;     // 8 keyframes per call: 16 images in one pyramid call
         lim.max_pts = 8; lim.max_corners = 8;
         kernels_.reset(new K(lim));
+        if (color_input_ && kernels_->colour_reserve(8) != 0)                   // one plane per keyframe of a call
+            throw SLAMException(std::string("DenseReconstruction: ") + kernels_->last_error());
     }
     std::string config_file_path_, slam_output_dir_, data_sequence_path_, map_file_;
     ConfigFile config_;
     int left_cam_index_ = 0, right_cam_index_ = 1, left_camera_index_in_slam_ = 0;
     int num_disparities_ = 128, blockSize_ = 15;   // include/StereoVisionSLAM/dense_reconstruction.h:56-57
     bool cloud_filters_ = false;                   // dense config `cloud_filters`: the PCL filters of :175-209
+    bool color_input_ = false;                     // dense config `is_color_input`: colour images in, a coloured cloud out
     svslam_bm_params params_;
     std::vector<DenseKeyframe> keyframes_;
     Dataset::Ptr dataset_;
     std::unique_ptr<K> kernels_;
     int src_w_ = 0, src_h_ = 0, w_ = 0, h_ = 0;
     std::vector<float> xyz_;                      // the merged cloud: x y z per point ...
-    std::vector<uint8_t> grey_;                   // ... and its grey value
+    std::vector<uint8_t> bgr_;                    // ... and its colour, b g r per point (grey input: three times the grey value)
 };
 
 } // namespace facade
