@@ -19,47 +19,32 @@ static int bm_check_params(svslam_ctx *c, const svslam_bm_params *p, BmParams &P
     return 0;
 }
 
-// rows per strip of k_stereo_bm: 16 amortise the 2r+1 rows a strip starts with; a call of few jobs takes shorter strips (8, 4) to
-// fill the device.  0 on stereobm.cpp's early-out (no column or no row to compute: every pixel FILTERED)
-static int bm_strip_rows(int w, int h, int njobs, const BmParams &P)
-{
-    const int r = P.bs / 2, x0 = P.nd - 1 + r, x1 = w - r, y0 = r, y1 = h - r;
-    if (x0 >= x1 || h < 2 * r + 1) return 0;
-    const int tiles = cdiv(x1 - x0, BM_TW);
-    int th = 16;
-    while (th > 4 && (long long)tiles * cdiv(y1 - y0, th) * njobs < 1024) th >>= 1;
-    return th;
-}
-
 int svslam_stereo_bm_strip_rows(svslam_ctx *c, int njobs, const svslam_bm_params *p)
 {
     if (!c) return -1;
     BmParams P;
     if (bm_check_params(c, p, P)) return -1;
     if (njobs <= 0 || njobs > c->lim.max_jobs) return fail(c, "stereo_bm: %d jobs out of [1, max_jobs]", njobs);
-    return bm_strip_rows(c->geom.w[0], c->geom.h[0], njobs, P);
+    return bm_plan(c->geom.w[0], c->geom.h[0], njobs, P).th;
 }
 
 // enqueue the matcher for njobs jobs (device array djobs) into c->bm.disp; no-op arithmetic when OpenCV's early-out applies
 static int launch_stereo_bm(svslam_ctx *c, int njobs, const BmJob *djobs, const BmParams &P)
 {
-    const int w = c->geom.w[0], h = c->geom.h[0], r = P.bs / 2;
-    if (!c->bm.disp) HIPCHK(c, hipMalloc(&c->bm.disp, sizeof(int16_t) * (size_t)w * h * c->lim.max_jobs));
-    const int x0 = P.nd - 1 + r, x1 = w - r, y0 = r, y1 = h - r;
-    const int th = bm_strip_rows(w, h, njobs, P);
-    const bool none = th == 0;
+    const int w = c->geom.w[0], h = c->geom.h[0];
+    if (c->bm.disp.reserve(c, "stereo_bm", sizeof(int16_t) * (size_t)w * h * c->lim.max_jobs, 0)) return -1;
+    int16_t *disp = (int16_t *)c->bm.disp.d;
+    const BmPlan pl = bm_plan(w, h, njobs, P);
     const size_t n = (size_t)w * h * njobs;
-    hipLaunchKernelGGL(k_bm_fill, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->stream, c->bm.disp, w, h, njobs,
-                       none ? 0 : x0, none ? 0 : x1, none ? 0 : y0, none ? 0 : y1);
-    if (!none) {
-        const dim3 grid(cdiv(x1 - x0, BM_TW), cdiv(y1 - y0, th), njobs);
-        const size_t lds = bm_lds_bytes(P.nd, P.bs, th);
+    hipLaunchKernelGGL(k_bm_fill, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->stream, disp, w, h, njobs, pl.x0, pl.x1, pl.y0, pl.y1);
+    if (pl.th) {
+        const dim3 grid(pl.tiles, pl.strips, njobs);
         switch ((P.bs + 3) / 4) {
-        case 2: hipLaunchKernelGGL(k_stereo_bm<2>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
-        case 3: hipLaunchKernelGGL(k_stereo_bm<3>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
-        case 4: hipLaunchKernelGGL(k_stereo_bm<4>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
-        case 5: hipLaunchKernelGGL(k_stereo_bm<5>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
-        default: hipLaunchKernelGGL(k_stereo_bm<6>, grid, dim3(BM_THREADS), lds, c->stream, djobs, c->d_pyr, c->geom, P, th, c->bm.disp); break;
+        case 2: hipLaunchKernelGGL(k_stereo_bm<2>, grid, dim3(BM_THREADS), pl.lds, c->stream, djobs, c->d_pyr, c->geom, P, pl.th, disp); break;
+        case 3: hipLaunchKernelGGL(k_stereo_bm<3>, grid, dim3(BM_THREADS), pl.lds, c->stream, djobs, c->d_pyr, c->geom, P, pl.th, disp); break;
+        case 4: hipLaunchKernelGGL(k_stereo_bm<4>, grid, dim3(BM_THREADS), pl.lds, c->stream, djobs, c->d_pyr, c->geom, P, pl.th, disp); break;
+        case 5: hipLaunchKernelGGL(k_stereo_bm<5>, grid, dim3(BM_THREADS), pl.lds, c->stream, djobs, c->d_pyr, c->geom, P, pl.th, disp); break;
+        default: hipLaunchKernelGGL(k_stereo_bm<6>, grid, dim3(BM_THREADS), pl.lds, c->stream, djobs, c->d_pyr, c->geom, P, pl.th, disp); break;
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -85,7 +70,7 @@ int svslam_stereo_bm_batch(svslam_ctx *c, int njobs, const svslam_bm_job *jobs, 
     const int rc = launch_stereo_bm(c, njobs, dp<BmJob>(c, ojobs), P);
     tm_end(c);
     if (rc) return -1;
-    HIPCHK(c, hipMemcpyAsync(out_disp, c->bm.disp, sizeof(int16_t) * (size_t)c->geom.w[0] * c->geom.h[0] * njobs, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_disp, c->bm.disp.d, sizeof(int16_t) * (size_t)c->geom.w[0] * c->geom.h[0] * njobs, hipMemcpyDeviceToHost, c->stream));
     if (d2h_sync(c, 0, 0)) return -1;
     return 0;
 }
@@ -119,10 +104,11 @@ static int dense_cloud_common(svslam_ctx *c, int njobs, svslam_dense_job *jobs, 
     const int w = c->geom.w[0], h = c->geom.h[0];
     const size_t N = (size_t)w * h;
     const int cap = (int)std::min<size_t>((size_t)max_pts_per_job, N);     // a job has at most w h survivors
-    const size_t bgr_per = ((size_t)3 * (size_t)(((cap + 3) / 4) * 4) + 15) & ~(size_t)15;      // k_colour_gather: 12 bytes per 4 points
+    const size_t bgr_per = col_bgr_per(cap);
     if (colour && c->col.bgr.reserve(c, "colour", bgr_per * (size_t)c->lim.max_jobs, 0)) return -1;
-    if (!c->bm.xyz) HIPCHK(c, hipMalloc(&c->bm.xyz, sizeof(float) * 3 * N * c->lim.max_jobs));
-    if (!c->bm.pix) HIPCHK(c, hipMalloc(&c->bm.pix, sizeof(int) * N * c->lim.max_jobs));
+    if (c->bm.xyz.reserve(c, "dense_cloud", sizeof(float) * 3 * N * c->lim.max_jobs, 0) || c->bm.pix.reserve(c, "dense_cloud", sizeof(int) * N * c->lim.max_jobs, 0)) return -1;
+    float *const d_xyz = (float *)c->bm.xyz.d;
+    int *const d_pix = (int *)c->bm.pix.d;
     c->ar.reset();
     static_assert(sizeof(DenseJob) == sizeof(svslam_dense_job), "job layout");
     const size_t obm = c->ar.take(sizeof(BmJob) * njobs);
@@ -139,11 +125,11 @@ static int dense_cloud_common(svslam_ctx *c, int njobs, svslam_dense_job *jobs, 
     cam.fxb = (float)cam_l[0] * (float)baseline;       // focal_length * baseline, both float (src/dense_reconstruction.cpp:120-124, 135)
     tm_begin(c, FAM_BM, njobs);
     const int rc = launch_stereo_bm(c, njobs, dp<BmJob>(c, obm), P);
-    if (!rc) hipLaunchKernelGGL(k_dense_cloud, dim3(njobs), dim3(DC_THREADS), 0, c->stream, dp<DenseJob>(c, oj), c->bm.disp, w, h, cam, cap, c->bm.xyz, c->bm.pix);
+    if (!rc) hipLaunchKernelGGL(k_dense_cloud, dim3(njobs), dim3(DC_THREADS), 0, c->stream, dp<DenseJob>(c, oj), (const int16_t *)c->bm.disp.d, w, h, cam, cap, d_xyz, d_pix);
     static_assert(sizeof(DenseJob) % sizeof(int) == 0 && offsetof(DenseJob, n_points) == 3 * sizeof(int), "n_points as k_colour_gather reads it");
     if (!rc && colour)
-        hipLaunchKernelGGL(k_colour_gather, dim3(cdiv(cdiv(cap, 4), COL_THREADS), njobs), dim3(COL_THREADS), 0, c->stream, dp<int>(c, oj) + 3,
-                           (int)(sizeof(DenseJob) / sizeof(int)), dp<int>(c, opl), (const int *)c->bm.pix, cap, (const uint8_t *)c->col.planes.d, 3 * N,
+        hipLaunchKernelGGL(k_colour_gather, dim3(col_gather_blocks(cap), njobs), dim3(COL_THREADS), 0, c->stream, dp<int>(c, oj) + 3,
+                           (int)(sizeof(DenseJob) / sizeof(int)), dp<int>(c, opl), (const int *)d_pix, cap, (const uint8_t *)c->col.planes.d, 3 * N,
                            (uint8_t *)c->col.bgr.d, bgr_per);
     tm_end(c);
     if (rc) return -1;
@@ -156,11 +142,11 @@ static int dense_cloud_common(svslam_ctx *c, int njobs, svslam_dense_job *jobs, 
     for (int i = 0; i < njobs; ++i) {
         const size_t n = (size_t)jobs[i].n_points;
         if (!n) continue;
-        HIPCHK(c, hipMemcpy(out_xyz + 3 * (size_t)jobs[i].pt_ofs, c->bm.xyz + 3 * (size_t)i * cap, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(out_pix + (size_t)jobs[i].pt_ofs, c->bm.pix + (size_t)i * cap, sizeof(int) * n, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(out_xyz + 3 * (size_t)jobs[i].pt_ofs, d_xyz + 3 * (size_t)i * cap, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(out_pix + (size_t)jobs[i].pt_ofs, d_pix + (size_t)i * cap, sizeof(int) * n, hipMemcpyDeviceToHost));
         if (colour) HIPCHK(c, hipMemcpy(out_bgr + 3 * (size_t)jobs[i].pt_ofs, c->col.bgr.d + (size_t)i * bgr_per, 3 * n, hipMemcpyDeviceToHost));
     }
-    if (out_disp_or_null) HIPCHK(c, hipMemcpy(out_disp_or_null, c->bm.disp, sizeof(int16_t) * N * njobs, hipMemcpyDeviceToHost));
+    if (out_disp_or_null) HIPCHK(c, hipMemcpy(out_disp_or_null, c->bm.disp.d, sizeof(int16_t) * N * njobs, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -243,15 +229,15 @@ int svslam_pyramid_bgr_batch(svslam_ctx *c, int n, const int *slots, const int *
         }
         HIPCHK(c, hipMemcpyAsync(c->img.d, c->img.pin, per * (size_t)n, hipMemcpyHostToDevice, c->stream));
     } else {
-        for (int i = 0; i < n; ++i) { bj[i].src = static_cast<const uint8_t *>(imgs[i]); bj[i].stride = decimate ? 2 * strides[i] : strides[i]; }
+        for (int i = 0; i < n; ++i) { bj[i].src = static_cast<const uint8_t *>(imgs[i]); bj[i].stride = col_row_stride(strides[i], decimate); }
     }
     for (int i = 0; i < n; ++i) {
         bj[i].plane = planes[i];
         pj[i].src = c->col.grey.d + grey_per * i; pj[i].src_stride = w; pj[i].slot = slots[i];
     }
     if (h2d(c, 0, c->ar.off)) return -1;
-    const int chunks = cdiv(w, COL_PX);
-    const dim3 grid(cdiv(h * chunks, COL_THREADS), n);
+    const int chunks = col_chunks(w);
+    const dim3 grid(col_prepare_blocks(w, h), n);
     tm_begin(c, FAM_COL, n);
     if (decimate) hipLaunchKernelGGL(k_bgr_prepare<true>, grid, dim3(COL_THREADS), 0, c->stream, dp<BgrJob>(c, ob), w, h, src_w, chunks, (uint8_t *)c->col.grey.d, grey_per, (uint8_t *)c->col.planes.d);
     else hipLaunchKernelGGL(k_bgr_prepare<false>, grid, dim3(COL_THREADS), 0, c->stream, dp<BgrJob>(c, ob), w, h, src_w, chunks, (uint8_t *)c->col.grey.d, grey_per, (uint8_t *)c->col.planes.d);
@@ -294,26 +280,10 @@ int svslam_cloud_sor_batch(svslam_ctx *c, int nseg, const int64_t *seg_ofs, cons
     if (nseg > 1 << 20) return fail(c, "cloud_filter: %d segments > 2^20", nseg);
     const int total = (int)total64;
     if (total && (!xyz || !out_keep)) return fail(c, "cloud_filter: null xyz / out_keep");
-    // one host pass: every coordinate finite (PCL's branch for the others is not restated), the box of every segment
     std::vector<CfSeg> segs((size_t)nseg);
     bool any = false;
-    for (int s = 0; s < nseg; ++s) {
-        CfSeg &g = segs[(size_t)s];
-        g.ofs = (int)(seg_ofs[s] - first); g.n = (int)(seg_ofs[s + 1] - seg_ofs[s]); g.pad = 0;
-        float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
-        const float *p = xyz + 3 * (size_t)seg_ofs[s];
-        for (int i = 0; i < g.n; ++i, p += 3) {
-            if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]))
-                return fail(c, "cloud_filter: point %d of segment %d has a non-finite coordinate", i, s);
-            for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], p[a]); mx[a] = std::max(mx[a], p[a]); }
-        }
-        float ext = 0.f;
-        for (int a = 0; a < 3; ++a) { g.mn[a] = g.n ? mn[a] : 0.f; if (g.n) ext = std::max(ext, mx[a] - mn[a]); }
-        g.inv_h = ext > 0.f ? 1024.0f / ext : 0.f;
-        if (!std::isfinite(g.inv_h)) g.inv_h = 0.f;
-        g.h = g.inv_h > 0.f ? 1.0f / g.inv_h : 0.f;
-        any = any || g.n >= mean_k + 1;
-    }
+    char msg[CF_MSG];
+    if (const char *e = cf_segments(nseg, seg_ofs, xyz, mean_k, segs.data(), &any, msg)) return fail(c, "%s", e);
     std::vector<float> md_own;
     if (!out_mean_dist_or_null) md_own.resize((size_t)std::max(total, 1));
     float *mdv = out_mean_dist_or_null ? out_mean_dist_or_null + first : md_own.data();       // mean distance of point seg_ofs[0] + i
@@ -322,8 +292,8 @@ int svslam_cloud_sor_batch(svslam_ctx *c, int nseg, const int64_t *seg_ofs, cons
         const size_t N = (size_t)total;
         auto &f = c->cf;
         if (cf_reserve(c, f.xyz, 12 * N) || cf_reserve(c, f.segs, sizeof(CfSeg) * (size_t)nseg) || cf_reserve(c, f.keys, 8 * N) || cf_reserve(c, f.keys2, 8 * N) ||
-            cf_reserve(c, f.vals, 4 * N) || cf_reserve(c, f.vals2, 4 * N) || cf_reserve(c, f.soa, 12 * N) || cf_reserve(c, f.out, 4 * N)) return -1;
-        if (!f.climbs) { HIPCHK(c, hipMalloc(&f.climbs, sizeof(unsigned))); }
+            cf_reserve(c, f.vals, 4 * N) || cf_reserve(c, f.vals2, 4 * N) || cf_reserve(c, f.soa, 12 * N) || cf_reserve(c, f.out, 4 * N) || f.climbs.reserve(c, "cloud_filter", sizeof(unsigned), 0)) return -1;
+        unsigned *const climbs = (unsigned *)f.climbs.d;
         int seg_bits = 1;
         while ((1 << seg_bits) < nseg) ++seg_bits;
         size_t tmp_bytes = 0;
@@ -332,7 +302,7 @@ int svslam_cloud_sor_batch(svslam_ctx *c, int nseg, const int64_t *seg_ofs, cons
         if (cf_reserve(c, f.tmp, tmp_bytes)) return -1;
         HIPCHK(c, hipMemcpy(f.xyz.d, xyz + 3 * (size_t)first, 12 * N, hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(f.segs.d, segs.data(), sizeof(CfSeg) * (size_t)nseg, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemsetAsync(f.climbs, 0, sizeof(unsigned), c->stream));
+        HIPCHK(c, hipMemsetAsync(climbs, 0, sizeof(unsigned), c->stream));
         float *sx = (float *)f.soa.d, *sy = sx + N, *sz = sy + N;
         tm_begin(c, FAM_CF, total);
         hipLaunchKernelGGL(k_cf_keys, cf_grid(total), dim3(CF_THREADS), 0, c->stream, (const float *)f.xyz.d, total, (const CfSeg *)f.segs.d, nseg,
@@ -343,36 +313,20 @@ int svslam_cloud_sor_batch(svslam_ctx *c, int nseg, const int64_t *seg_ofs, cons
         // 51 register slots hold the reference's k = 50; a larger k takes the 65-slot instance
         if (mean_k <= 50)
             hipLaunchKernelGGL(k_cf_knn<51>, cf_grid(total), dim3(CF_THREADS), 0, c->stream, (const unsigned long long *)f.keys2.d, (const unsigned *)f.vals2.d,
-                               (const float *)sx, (const float *)sy, (const float *)sz, total, (const CfSeg *)f.segs.d, mean_k, (float *)f.out.d, f.climbs);
+                               (const float *)sx, (const float *)sy, (const float *)sz, total, (const CfSeg *)f.segs.d, mean_k, (float *)f.out.d, climbs);
         else
             hipLaunchKernelGGL(k_cf_knn<CF_KMAX + 1>, cf_grid(total), dim3(CF_THREADS), 0, c->stream, (const unsigned long long *)f.keys2.d, (const unsigned *)f.vals2.d,
-                               (const float *)sx, (const float *)sy, (const float *)sz, total, (const CfSeg *)f.segs.d, mean_k, (float *)f.out.d, f.climbs);
+                               (const float *)sx, (const float *)sy, (const float *)sz, total, (const CfSeg *)f.segs.d, mean_k, (float *)f.out.d, climbs);
         tm_end(c);
         HIPCHK(c, hipGetLastError());
         if (d2h_sync(c, 0, 0)) return -1;
         HIPCHK(c, hipMemcpy(mdv, f.out.d, 4 * N, hipMemcpyDeviceToHost));
         unsigned climbed = 0;
-        HIPCHK(c, hipMemcpy(&climbed, f.climbs, sizeof(unsigned), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(&climbed, climbs, sizeof(unsigned), hipMemcpyDeviceToHost));
         for (const CfSeg &g : segs) if (g.n >= mean_k + 1) f.queries += g.n;
         f.climbed += climbed;
     }
-    // PCL's statistics on the host, sequentially in index order: the threshold has the yardstick's bits by construction
-    for (int s = 0; s < nseg; ++s) {
-        const CfSeg &g = segs[(size_t)s];
-        const float *d = mdv + g.ofs;
-        uint8_t *keep = out_keep + seg_ofs[s];
-        if (g.n < mean_k + 1) {                            // no valid distance: 0 / 0, nothing is above a NaN
-            out_threshold[s] = std::nan("");
-            for (int i = 0; i < g.n; ++i) keep[i] = 1;
-            continue;
-        }
-        double sum = 0.0, sq_sum = 0.0;
-        for (int i = 0; i < g.n; ++i) { sum += (double)d[i]; const float sq = d[i] * d[i]; sq_sum += (double)sq; }
-        const double nv = (double)g.n, mean = sum / nv, var = (sq_sum - sum * sum / nv) / (nv - 1.0);
-        const double thr = mean + stddev_mul * std::sqrt(var);
-        out_threshold[s] = thr;
-        for (int i = 0; i < g.n; ++i) keep[i] = !((double)d[i] > thr) ? 1 : 0;
-    }
+    for (int s = 0; s < nseg; ++s) out_threshold[s] = cf_sor_decide(segs[(size_t)s].n, mdv + segs[(size_t)s].ofs, mean_k, stddev_mul, out_keep + seg_ofs[s]);
     return 0;
 }
 
@@ -396,35 +350,15 @@ int svslam_cloud_voxel_grid(svslam_ctx *c, int64_t n, const float *xyz, const ui
     if (n == 0) return 0;
     if (!xyz || !rgb || !out_xyz || !out_rgb) return fail(c, "cloud_filter: null cloud / output");
     const size_t N = (size_t)n;
-    float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
-    for (size_t i = 0; i < N; ++i)
-        for (int a = 0; a < 3; ++a) {
-            const float v = xyz[3 * i + a];
-            if (!std::isfinite(v)) return fail(c, "cloud_filter: point %zu has a non-finite coordinate", i);
-            mn[a] = std::min(mn[a], v); mx[a] = std::max(mx[a], v);
-        }
     VgParams P;
-    P.inv = 1.0f / (float)leaf;
-    if (!std::isfinite(P.inv) || !(P.inv > 0.f)) return fail(c, "cloud_filter: leaf %g has no float reciprocal", leaf);
-    // PCL's guard: more than INT32_MAX cells -> "Leaf size is too small for the input dataset", the output is the input
-    int64_t cells[3];
     bool over = false;
-    for (int a = 0; a < 3; ++a) {
-        const float e = (mx[a] - mn[a]) * P.inv;
-        if (!(e < 9.0e18f)) over = true; else cells[a] = (int64_t)e + 1;
-    }
-    if (!over) over = (__int128)cells[0] * cells[1] * cells[2] > (__int128)INT32_MAX;
+    char msg[CF_MSG];
+    if (const char *e = vg_plan(N, xyz, leaf, P, &over, msg)) return fail(c, "%s", e);
     if (over) {
         memcpy(out_xyz, xyz, 12 * N); memcpy(out_rgb, rgb, 3 * N);
         *out_n = n; *out_overflowed = 1;
         return 0;
     }
-    int max_b[3], div_b[3];
-    for (int a = 0; a < 3; ++a) {
-        P.min_b[a] = (int)std::floor(mn[a] * P.inv); max_b[a] = (int)std::floor(mx[a] * P.inv);
-        div_b[a] = max_b[a] - P.min_b[a] + 1;
-    }
-    P.mul[0] = 1; P.mul[1] = div_b[0]; P.mul[2] = (int)((unsigned)div_b[0] * (unsigned)div_b[1]);
     auto &f = c->cf;
     if (cf_reserve(c, f.xyz, 12 * N) || cf_reserve(c, f.rgb, 3 * N) || cf_reserve(c, f.keys, 8 * N) || cf_reserve(c, f.keys2, 8 * N) || cf_reserve(c, f.flag, 4 * N) ||
         cf_reserve(c, f.pos, 4 * N) || cf_reserve(c, f.start, 4 * N) || cf_reserve(c, f.oxyz, 12 * N) || cf_reserve(c, f.orgb, 3 * N)) return -1;

@@ -17,16 +17,7 @@
 #endif
 
 #define SVS_WAVE 64
-#define SVS_BORDER 16          // stored REFLECT_101 border of every pyramid level
-#define SVS_LEVELS 4
-
-struct PyrGeom {
-    int w[SVS_LEVELS], h[SVS_LEVELS];
-    int pitch[SVS_LEVELS];          // bytes per padded row
-    size_t ofs[SVS_LEVELS];         // byte offset of the padded level inside a slot
-    size_t slot_bytes;
-    int nlevels;
-};
+#include "pyr_geom.h"          // SVS_BORDER, SVS_LEVELS, PyrGeom, lvl_origin
 
 __device__ __forceinline__ int reflect101(int p, int len)
 {
@@ -37,16 +28,6 @@ __device__ __forceinline__ int reflect101(int p, int len)
         else p = 2 * len - 2 - p;
     }
     return p;
-}
-
-// pixel (0,0) of level l in a slot
-__device__ __forceinline__ const uint8_t *lvl_origin(const uint8_t *slot, const PyrGeom &g, int l)
-{
-    return slot + g.ofs[l] + (size_t)SVS_BORDER * g.pitch[l] + SVS_BORDER;
-}
-__device__ __forceinline__ uint8_t *lvl_origin(uint8_t *slot, const PyrGeom &g, int l)
-{
-    return slot + g.ofs[l] + (size_t)SVS_BORDER * g.pitch[l] + SVS_BORDER;
 }
 
 // ---- wave reductions (all lanes end with the total) -------------------

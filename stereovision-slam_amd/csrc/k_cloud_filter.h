@@ -20,15 +20,97 @@
 // q' >= Q has t' >= Q, so u' >= Q h (1 - 2^-23) and p' - p >= Q h - u - 3 * 2^-23 * 1024 h; what f32 evaluation of Q h - u adds
 // is of the same size (every term is <= 1024 h).  0.01 h is taken off (25 x those together) and the square is scaled by
 // 1 - 1e-5 for its own roundings; a computed squared distance is never below the computed square of one of its axes.
+//
+// The host's part (cf_segments, cf_sor_decide, vg_plan) is plain C++ here too: api_dense.h and the host emulation call the same
+// functions.  A refusal is the message, written into the caller's `msg` (CF_MSG bytes); nullptr otherwise.
 #pragma once
 #pragma clang fp contract(off)
+#include <stdint.h>
+#include <stdio.h>
+#include <algorithm>
+#include <cmath>
 
 #define CF_THREADS 256
 #define CF_KMAX 64                 /* mean_k of svslam_cloud_sor_batch: 1 .. 64 */
 #define CF_MORTON_MASK 0x3FFFFFFFull
+#define CF_MSG 128
 
 struct CfSeg { int ofs, n; float mn[3]; float inv_h, h; int pad; };       // a segment of the batch: points [ofs, ofs + n), its box and cell
 struct VgParams { float inv; int min_b[3]; int mul[3]; };
+
+// One host pass over the batch (points seg_ofs[0] .. seg_ofs[nseg] of xyz): every coordinate finite (PCL's branch for the others is not
+// restated), the box and the cell of every segment; *any: some segment has the mean_k + 1 points a search needs
+inline const char *cf_segments(int nseg, const int64_t *seg_ofs, const float *xyz, int mean_k, CfSeg *out, bool *any, char *msg)
+{
+    *any = false;
+    for (int s = 0; s < nseg; ++s) {
+        CfSeg &g = out[s];
+        g.ofs = (int)(seg_ofs[s] - seg_ofs[0]); g.n = (int)(seg_ofs[s + 1] - seg_ofs[s]); g.pad = 0;
+        float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
+        const float *p = xyz + 3 * (size_t)seg_ofs[s];
+        for (int i = 0; i < g.n; ++i, p += 3) {
+            if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) {
+                snprintf(msg, CF_MSG, "cloud_filter: point %d of segment %d has a non-finite coordinate", i, s);
+                return msg;
+            }
+            for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], p[a]); mx[a] = std::max(mx[a], p[a]); }
+        }
+        float ext = 0.f;
+        for (int a = 0; a < 3; ++a) { g.mn[a] = g.n ? mn[a] : 0.f; if (g.n) ext = std::max(ext, mx[a] - mn[a]); }
+        g.inv_h = ext > 0.f ? 1024.0f / ext : 0.f;
+        if (!std::isfinite(g.inv_h)) g.inv_h = 0.f;
+        g.h = g.inv_h > 0.f ? 1.0f / g.inv_h : 0.f;
+        *any = *any || g.n >= mean_k + 1;
+    }
+    return nullptr;
+}
+
+// PCL's statistics over the n mean distances of a segment, sequentially in index order: the threshold has the yardstick's bits by
+// construction.  Returns the threshold, keep[i] = the point stays
+inline double cf_sor_decide(int n, const float *d, int mean_k, double stddev_mul, uint8_t *keep)
+{
+    if (n < mean_k + 1) {                                  // no valid distance: 0 / 0, nothing is above a NaN
+        for (int i = 0; i < n; ++i) keep[i] = 1;
+        return std::nan("");
+    }
+    double sum = 0.0, sq_sum = 0.0;
+    for (int i = 0; i < n; ++i) { sum += (double)d[i]; const float sq = d[i] * d[i]; sq_sum += (double)sq; }
+    const double nv = (double)n, mean = sum / nv, var = (sq_sum - sum * sum / nv) / (nv - 1.0);
+    const double thr = mean + stddev_mul * std::sqrt(var);
+    for (int i = 0; i < n; ++i) keep[i] = !((double)d[i] > thr) ? 1 : 0;
+    return thr;
+}
+
+// pcl::VoxelGrid's set-up for n points and a leaf > 0: the float reciprocal, the box, PCL's guard (*over: more than INT32_MAX cells ->
+// "Leaf size is too small for the input dataset", the output is the input; P.min_b and P.mul are not set then), the index origin
+// and the multipliers
+inline const char *vg_plan(size_t n, const float *xyz, double leaf, VgParams &P, bool *over, char *msg)
+{
+    float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for (size_t i = 0; i < n; ++i)
+        for (int a = 0; a < 3; ++a) {
+            const float v = xyz[3 * i + a];
+            if (!std::isfinite(v)) { snprintf(msg, CF_MSG, "cloud_filter: point %zu has a non-finite coordinate", i); return msg; }
+            mn[a] = std::min(mn[a], v); mx[a] = std::max(mx[a], v);
+        }
+    P.inv = 1.0f / (float)leaf;
+    if (!std::isfinite(P.inv) || !(P.inv > 0.f)) { snprintf(msg, CF_MSG, "cloud_filter: leaf %g has no float reciprocal", leaf); return msg; }
+    int64_t cells[3];
+    *over = false;
+    for (int a = 0; a < 3; ++a) {
+        const float e = (mx[a] - mn[a]) * P.inv;
+        if (!(e < 9.0e18f)) *over = true; else cells[a] = (int64_t)e + 1;
+    }
+    if (!*over) *over = (__int128)cells[0] * cells[1] * cells[2] > (__int128)INT32_MAX;
+    if (*over) return nullptr;
+    int div_b[3];
+    for (int a = 0; a < 3; ++a) {
+        P.min_b[a] = (int)std::floor(mn[a] * P.inv);
+        div_b[a] = (int)std::floor(mx[a] * P.inv) - P.min_b[a] + 1;
+    }
+    P.mul[0] = 1; P.mul[1] = div_b[0]; P.mul[2] = (int)((unsigned)div_b[0] * (unsigned)div_b[1]);
+    return nullptr;
+}
 
 __device__ __forceinline__ int cf_cell(float p, float mn, float inv_h)
 {

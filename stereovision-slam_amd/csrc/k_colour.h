@@ -27,6 +27,13 @@ struct BgrJob {
 #define COL_THREADS 256
 #define COL_PX 16         // output pixels per thread
 
+// the sizes a caller and the kernels agree on (host): pieces of a row, grid.x of the two kernels, BgrJob::stride, out_per
+inline int col_chunks(int w) { return (w + COL_PX - 1) / COL_PX; }
+inline unsigned col_prepare_blocks(int w, int h) { return (unsigned)((h * col_chunks(w) + COL_THREADS - 1) / COL_THREADS); }
+inline unsigned col_gather_blocks(int max_pts) { return (unsigned)(((max_pts + 3) / 4 + COL_THREADS - 1) / COL_THREADS); }
+inline int col_row_stride(int pitch, bool decimate) { return decimate ? 2 * pitch : pitch; }
+inline size_t col_bgr_per(int max_pts) { return ((size_t)3 * (size_t)(((max_pts + 3) / 4) * 4) + 15) & ~(size_t)15; }      // 12 bytes per 4 points
+
 struct ColQ { uint32_t x, y, z, w; };
 #if defined(__HIPCC__)
 typedef uint32_t col_u4v __attribute__((ext_vector_type(4)));

@@ -14,8 +14,19 @@
 // horizontal row sums H(x, d, row) slide vertically in registers: S += H(new row) - H(old row).  Per output row the
 // nd sums of every column go to LDS (u16 pairs); min / arg-min (ties to the LARGEST d), the uniqueness scan, the texture
 // sum (wave 0, same machinery against the cap byte) and the sub-pixel step follow from there.
+//
+// BM_HOST_EMU (tests/cpp/bm_host_emu, after tests/cpp/hip_on_host.h): the matcher half of this file under g++ as it stands.  LDS is
+// the emulation's heap block, the two byte instructions are its functions, the cloud half (d_quat_rot) is left out.
 #pragma once
+#ifdef BM_HOST_EMU
+#include "pyr_geom.h"
+#define BM_LDS(name) unsigned int *name = emu_lds
+#define __builtin_amdgcn_alignbyte emu_alignbyte
+#define __builtin_amdgcn_sad_u8 emu_sad_u8
+#else
 #include "dev_common.h"
+#define BM_LDS(name) extern __shared__ unsigned int name[]
+#endif
 
 #define BM_TW 64
 #define BM_THREADS 256
@@ -33,6 +44,23 @@ __host__ __device__ inline size_t bm_lds_bytes(int nd, int bs, int th)
     return (size_t)srows * (bm_pitch_l(nww) + bm_pitch_r(nd, nww)) + (size_t)(nd / 2) * BM_TW * 4 + 4 * BM_TW * 8 + 2 * BM_TW * 4;
 }
 
+// What a call of njobs jobs on w x h images launches.  [x0, x1) x [y0, y1) is the window cv::StereoBM computes, k_bm_fill's argument:
+// empty, and th 0, on stereobm.cpp's early-out (no column or no row to compute: every pixel FILTERED).  th = rows per strip of
+// k_stereo_bm: 16 amortise the 2r+1 rows a strip starts with; a call of fewer than 1024 workgroups takes shorter strips (8, 4) to
+// fill the device.  The grid is (tiles, strips, njobs), lds the dynamic LDS of a workgroup.
+struct BmPlan { int x0, x1, y0, y1, th, tiles, strips; size_t lds; };
+inline BmPlan bm_plan(int w, int h, int njobs, const BmParams &P)
+{
+    const int r = P.bs / 2;
+    BmPlan p = { P.nd - 1 + r, w - r, r, h - r, 0, 0, 0, 0 };
+    if (p.x0 >= p.x1 || h < 2 * r + 1) { p.x0 = p.x1 = p.y0 = p.y1 = 0; return p; }
+    p.tiles = (p.x1 - p.x0 + BM_TW - 1) / BM_TW;
+    p.th = 32;
+    do { p.th >>= 1; p.strips = (p.y1 - p.y0 + p.th - 1) / p.th; } while (p.th > 4 && (long long)p.tiles * p.strips * njobs < 1024);
+    p.lds = bm_lds_bytes(P.nd, P.bs, p.th);
+    return p;
+}
+
 // one pixel of cv::prefilterXSobel: rows outside the image reflect without repeating the edge, columns 0 and w-1 and an
 // unpaired last row are cap
 __device__ __forceinline__ int bm_prefilter(const uint8_t *img, int pitch, int w, int h, int x, int y, int cap)
@@ -44,19 +72,22 @@ __device__ __forceinline__ int bm_prefilter(const uint8_t *img, int pitch, int w
     return min(max(v, -cap), cap) + cap;
 }
 
+// element i of the njobs disparity images: FILTERED unless the matcher computes it
+__device__ __forceinline__ void bm_fill_one(int16_t *out, size_t i, int w, int h, int x0, int x1, int y0, int y1)
+{
+    const int p = (int)(i % ((size_t)w * h)), y = p / w, x = p - y * w;
+    if (!(x >= x0 && x < x1 && y >= y0 && y < y1)) out[i] = BM_FILTERED;
+}
 __global__ void k_bm_fill(int16_t *out, int w, int h, int njobs, int x0, int x1, int y0, int y1)
 {
     const size_t n = (size_t)w * h * njobs;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int p = (int)(i % ((size_t)w * h)), y = p / w, x = p - y * w;
-        if (!(x >= x0 && x < x1 && y >= y0 && y < y1)) out[i] = BM_FILTERED;
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) bm_fill_one(out, i, w, h, x0, x1, y0, y1);
 }
 
 template <int NWW>
 __global__ __launch_bounds__(BM_THREADS) void k_stereo_bm(const BmJob *jobs, const uint8_t *pyr, PyrGeom g, BmParams P, int th, int16_t *out)
 {
-    extern __shared__ unsigned int bm_lds[];
+    BM_LDS(bm_lds);
     const int w = g.w[0], h = g.h[0], nd = P.nd, r = P.bs >> 1, cap = P.cap;
     const int tid = threadIdx.x, xi = tid & 63, wv = tid >> 6;
     const int x0 = nd - 1 + r + (int)blockIdx.x * BM_TW;         // first output column of the tile (< w - r by the grid)
@@ -214,6 +245,7 @@ __global__ __launch_bounds__(BM_THREADS) void k_stereo_bm(const BmJob *jobs, con
     }
 }
 
+#ifndef BM_HOST_EMU
 // ---- the cloud (src/dense_reconstruction.cpp:116-173 with its types) --------------------------------------------------
 struct DenseJob { int slot_left, slot_right, pt_ofs, n_points; double T_cw[7]; };
 struct DenseCam { double fx, fy, cx, cy, ext[7], min_depth; float fxb; };       // fxb = (float)fx * (float)baseline
@@ -276,3 +308,4 @@ __global__ __launch_bounds__(DC_THREADS) void k_dense_cloud(DenseJob *jobs, cons
     }
 }
 #pragma clang fp contract(off)
+#endif

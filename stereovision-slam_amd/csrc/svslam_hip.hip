@@ -128,9 +128,9 @@ struct svslam_ctx {
     // GFTT scratch
     GfttWork gw;
     // dense stereo scratch (svslam_stereo_bm_batch / svslam_dense_cloud_batch), allocated at first use for max_jobs images
-    struct { int16_t *disp = nullptr; float *xyz = nullptr; int *pix = nullptr; } bm;
+    struct { DevBuf disp, xyz, pix; } bm;
     // cloud filters (svslam_cloud_sor_batch / svslam_cloud_voxel_grid): device buffers sized at first use, grown on demand
-    struct { DevBuf xyz, rgb, segs, keys, keys2, vals, vals2, soa, out, flag, pos, start, oxyz, orgb, tmp; unsigned *climbs = nullptr;
+    struct { DevBuf xyz, rgb, segs, keys, keys2, vals, vals2, soa, out, flag, pos, start, oxyz, orgb, tmp, climbs;
              long long queries = 0, climbed = 0; } cf;
     // pose graph (svslam_pose_graph_batch): one device buffer (inputs, results, solver scratch) and its pageable host mirror of the
     // uploaded part, sized at first use, grown on demand and kept
@@ -798,8 +798,6 @@ void svslam_destroy(svslam_ctx *c)
         (void)hipFree(c->gw.prof);
     }
     (void)hipFree(c->gw.keys); (void)hipFree(c->gw.counters);
-    (void)hipFree(c->bm.disp); (void)hipFree(c->bm.xyz); (void)hipFree(c->bm.pix);
-    (void)hipFree(c->cf.climbs);
     (void)hipFree(c->lc.S.rows); (void)hipFree(c->lc.S.ids);
     (void)hipFree(c->gd.d_prm); (void)hipFree(c->gd.d_tab);
     ba_work_free(c->bw);

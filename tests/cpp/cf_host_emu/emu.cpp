@@ -1,39 +1,27 @@
 // csrc/k_cloud_filter.h compiled for the host (tests/test_host_emulation_cloud_filters.py): the HIP qualifiers vanish, a "thread" is a
 // call of the per-thread function, the two radix sorts are std::sort.  The kernels of that file use no LDS and no cross-lane
-// operation, so the emulation is a loop.  The segment set-up (box, cell size) restates the few host lines of
-// svslam_cloud_sor_batch.
-#include <stdint.h>
-#include <stddef.h>
-#include <algorithm>
-#include <cmath>
+// operation, so the emulation is a loop.  The segment set-up, the statistics and the voxel plan are the file's own host functions,
+// the ones svslam_cloud_sor_batch and svslam_cloud_voxel_grid call.
+#include "../hip_on_host.h"
 #include <numeric>
 #include <vector>
-using std::min; using std::max;
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-struct Dim3 { unsigned x, y, z; };
 static Dim3 threadIdx, blockIdx;
-static inline unsigned atomicAdd(unsigned *p, unsigned v) { const unsigned o = *p; *p += v; return o; }
 #include "../../../stereovision-slam_amd/csrc/k_cloud_filter.h"
 
-extern "C" int emu_sor_mean_dist(int nseg, const long long *seg_ofs, const float *xyz, int k, float *out_md, unsigned *out_climbs)
+static char g_msg[CF_MSG];
+extern "C" const char *emu_cf_error() { return g_msg; }
+
+extern "C" double emu_cf_sor_decide(int n, const float *d, int k, double stddev_mul, uint8_t *keep) { return cf_sor_decide(n, d, k, stddev_mul, keep); }
+
+// out_md: mean distance of point seg_ofs[0] + i at [i]; with out_segs the set-up alone (segs[nseg], any).  -1 and emu_cf_error(): refused
+extern "C" int emu_sor_mean_dist(int nseg, const int64_t *seg_ofs, const float *xyz_all, int k, float *out_md, unsigned *out_climbs, CfSeg *out_segs, int *out_any)
 {
-    const int total = (int)seg_ofs[nseg];
+    const int total = (int)(seg_ofs[nseg] - seg_ofs[0]);
     std::vector<CfSeg> segs((size_t)nseg);
-    for (int s = 0; s < nseg; ++s) {
-        CfSeg &g = segs[(size_t)s];
-        g.ofs = (int)seg_ofs[s]; g.n = (int)(seg_ofs[s + 1] - seg_ofs[s]); g.pad = 0;
-        float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
-        for (int i = 0; i < g.n; ++i)
-            for (int a = 0; a < 3; ++a) { const float v = xyz[3 * (size_t)(g.ofs + i) + a]; mn[a] = std::min(mn[a], v); mx[a] = std::max(mx[a], v); }
-        float ext = 0.f;
-        for (int a = 0; a < 3; ++a) { g.mn[a] = g.n ? mn[a] : 0.f; if (g.n) ext = std::max(ext, mx[a] - mn[a]); }
-        g.inv_h = ext > 0.f ? 1024.0f / ext : 0.f;
-        if (!std::isfinite(g.inv_h)) g.inv_h = 0.f;
-        g.h = g.inv_h > 0.f ? 1.0f / g.inv_h : 0.f;
-    }
+    bool any = false;
+    if (cf_segments(nseg, seg_ofs, xyz_all, k, segs.data(), &any, g_msg)) return -1;
+    if (out_segs) { std::copy(segs.begin(), segs.end(), out_segs); *out_any = any; return 0; }
+    const float *xyz = xyz_all + 3 * (size_t)seg_ofs[0];
     std::vector<unsigned long long> keys((size_t)total), skeys((size_t)total);
     std::vector<unsigned> vals((size_t)total), perm((size_t)total);
     for (int i = 0; i < total; ++i) cf_keys_one(i, xyz, segs.data(), nseg, keys.data(), vals.data());
@@ -52,11 +40,14 @@ extern "C" int emu_sor_mean_dist(int nseg, const long long *seg_ofs, const float
     return 0;
 }
 
-extern "C" int emu_voxel_grid(int n, const float *xyz, const uint8_t *rgb, float inv, const int *min_b, const int *mul, float *out_xyz, uint8_t *out_rgb)
+// the voxel grid on the library's plan (*plan), the plan alone without out_xyz; -1 and emu_cf_error(): refused, -2: PCL's guard
+extern "C" int emu_voxel_grid(int n, const float *xyz, const uint8_t *rgb, double leaf, VgParams *plan, float *out_xyz, uint8_t *out_rgb)
 {
-    VgParams P;
-    P.inv = inv;
-    for (int a = 0; a < 3; ++a) { P.min_b[a] = min_b[a]; P.mul[a] = mul[a]; }
+    VgParams &P = *plan;
+    bool over = false;
+    if (vg_plan((size_t)n, xyz, leaf, P, &over, g_msg)) return -1;
+    if (over) return -2;
+    if (!out_xyz) return 0;
     std::vector<unsigned long long> keys((size_t)n);
     for (int i = 0; i < n; ++i) vg_keys_one(i, xyz, P, keys.data());
     std::sort(keys.begin(), keys.end());

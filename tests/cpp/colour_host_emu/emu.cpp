@@ -3,15 +3,7 @@
 // The kernels of that file use no LDS and no cross-lane operation, so the emulation is a loop.  The 16-byte loads and stores are
 // memcpy here; the source is copied into a heap block of exactly stride * (rows - 1) + 3 * src_w bytes first: the bytes the ABI
 // promises to stay within, and no more.
-#include <stdint.h>
-#include <stddef.h>
-#include <stdlib.h>
-#include <string.h>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-struct Dim3 { unsigned x, y, z; };
+#include "../hip_on_host.h"
 static Dim3 threadIdx, blockIdx;
 #include "../../../stereovision-slam_amd/csrc/k_colour.h"
 
@@ -24,9 +16,8 @@ extern "C" int emu_bgr_prepare(const uint8_t *src, int stride, int src_w, int sr
     if (!own) return -1;
     memcpy(own, src, bytes);
     BgrJob jb;
-    jb.src = own; jb.stride = dec ? 2 * stride : stride; jb.plane = plane;
-    const int chunks = (w + COL_PX - 1) / COL_PX;
-    const int nblk = (h * chunks + COL_THREADS - 1) / COL_THREADS;
+    jb.src = own; jb.stride = col_row_stride(stride, dec); jb.plane = plane;
+    const int chunks = col_chunks(w), nblk = (int)col_prepare_blocks(w, h);
     for (int t = 0; t < nblk * COL_THREADS; ++t) {
         if (dec) bgr_prepare_task<true>(jb, 0, t, w, h, src_w, chunks, grey, (size_t)w * h, planes);
         else bgr_prepare_task<false>(jb, 0, t, w, h, src_w, chunks, grey, (size_t)w * h, planes);
@@ -35,11 +26,13 @@ extern "C" int emu_bgr_prepare(const uint8_t *src, int stride, int src_w, int sr
     return 0;
 }
 
+extern "C" size_t emu_colour_bgr_per(int max_pts) { return col_bgr_per(max_pts); }
+
 // n_points[njobs], plane_of[njobs], pix [njobs][max_pts], planes [nplanes][plane_bytes], out [njobs][out_per]
 extern "C" int emu_colour_gather(int njobs, const int *n_points, const int *plane_of, const int *pix, int max_pts, const uint8_t *planes,
                                  size_t plane_bytes, uint8_t *out, size_t out_per)
 {
-    const int quads = (max_pts + 3) / 4, nblk = (quads + COL_THREADS - 1) / COL_THREADS;
+    const int nblk = (int)col_gather_blocks(max_pts);
     for (int j = 0; j < njobs; ++j)
         for (int i = 0; i < nblk * COL_THREADS; ++i) colour_gather_task(j, i, n_points, 1, plane_of, pix, max_pts, planes, plane_bytes, out, out_per);
     return 0;

@@ -4,8 +4,6 @@ neighbours."""
 import ctypes as C
 import importlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
@@ -39,13 +37,7 @@ def load_emu():
     """csrc/k_global_desc.h compiled for the host: the package's lib/libgd_host_emu.so when the build left it, else compiled here"""
     global _emu
     if _emu is None:
-        so = os.path.join(ROOT, "stereovision-slam_amd", "lib", "libgd_host_emu.so")
-        src = os.path.join(ROOT, "tests", "cpp", "gd_host_emu", "emu.cpp")
-        hdr = os.path.join(ROOT, "stereovision-slam_amd", "csrc", "k_global_desc.h")
-        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-            so = os.path.join(tempfile.mkdtemp(prefix="gd_host_emu"), "libgd_host_emu.so")
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", src, "-o", so])
-        L = C.CDLL(so)
+        L = C.CDLL(importlib.import_module("stereovision-slam_amd.build").build_emu("gd"))
         L.emu_gd_error.restype = C.c_char_p
         L.emu_gd_job_floats.restype = C.c_longlong
         L.emu_gd_configure.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]

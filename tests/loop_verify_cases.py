@@ -13,8 +13,7 @@ discrete outcomes comparable between implementations that round differently:
 A seed that violates a margin is replaced HERE (change the seed in CASES), never skipped at run time."""
 import ctypes as C
 import functools
-import os
-import subprocess
+import importlib
 
 import numpy as np
 
@@ -333,10 +332,7 @@ def rotations():
 # ---------------------------------------------------------------- the host emulation's ctypes side (tests/cpp/lv_host_emu)
 def emu_build(root, out_dir, opt="-O2"):
     """compiles tests/cpp/lv_host_emu/emu.cpp of the tree at `root` (the repository, or a copy with an edited kernel) into out_dir"""
-    so = os.path.join(str(out_dir), "liblv_host_emu.so")
-    subprocess.check_call(["g++", opt, "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                           os.path.join(str(root), "tests", "cpp", "lv_host_emu", "emu.cpp"), "-o", so])
-    return C.CDLL(so)
+    return C.CDLL(importlib.import_module("stereovision-slam_amd.build").build_emu("lv", root, out_dir, opt=opt))
 
 
 def check_draw4(lib):

@@ -485,9 +485,5 @@ def check_new_case(name, job, got, run, same_libm):
 def emu_build(src_root, out_dir, opt="-O2"):
     """tests/cpp/pg_host_emu of the tree at src_root as a shared library in out_dir (no contraction: the device code has none)"""
     import ctypes as C
-    import os
-    import subprocess
-    so = os.path.join(str(out_dir), "libpg_host_emu.so")
-    subprocess.check_call(["g++", opt, "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                           os.path.join(str(src_root), "tests", "cpp", "pg_host_emu", "emu.cpp"), "-o", so])
-    return C.CDLL(so)
+    import importlib
+    return C.CDLL(importlib.import_module("stereovision-slam_amd.build").build_emu("pg", src_root, out_dir, opt=opt))

@@ -3,8 +3,6 @@ of brief_cases.py, exactly: n_desc, desc_pt and every descriptor byte, and each 
 LDS layout, both blur passes, the tests and the packing are checked here without a device.  Not a replacement for
 tests/test_gpu_brief.py: the compiler, the ISA, the barriers, LDS and the launches are not in it."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,16 +10,10 @@ import pytest
 import brief_cases as bc
 import ref_brief as rb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU = os.path.join(ROOT, "tests", "cpp", "brief_host_emu")
-
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    d = tmp_path_factory.mktemp("brief_host_emu")
-    so = str(d / "libbrief_host_emu.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(EMU, "emu.cpp"), "-o", so])
-    return C.CDLL(so)
+def emu(svs):
+    return C.CDLL(svs._build.build_emu("brief"))
 
 
 def test_default_table_is_the_generated_one(emu):

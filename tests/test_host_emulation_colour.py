@@ -3,8 +3,6 @@ grey image, the plane, the decimation, the row tails and the gather, bit for bit
 tests/test_gpu_colour.py (the compiler, the ISA's unaligned 16-byte accesses and the launches are not in it); it is what makes a
 change of the kernel's indexing visible on a machine without a device."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,16 +10,11 @@ import pytest
 import ref_colour as rc
 from colour_cases import DEC_DOWN, DEC_UP, DIRECT, KITTI, stereo_pair, strided
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU = os.path.join(ROOT, "tests", "cpp", "colour_host_emu")
-
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    d = tmp_path_factory.mktemp("colour_host_emu")
-    so = str(d / "libcolour_host_emu.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unknown-pragmas", os.path.join(EMU, "emu.cpp"), "-o", so])
-    L = C.CDLL(so)
+def emu(svs):
+    L = C.CDLL(svs._build.build_emu("colour"))
+    L.emu_colour_bgr_per.restype = C.c_size_t
     L.emu_colour_gather.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     return L
 
@@ -73,7 +66,8 @@ def test_gather_source_on_the_host_equals_indexing(emu):
         counts = np.array([max_pts, max_pts - 1 if max_pts > 1 else 0, max_pts + 1, min(5, max_pts)], np.int32)     # job 2 overflowed: no list
         plane_of = np.array([2, 0, 1, 2], np.int32)
         pix = rng.integers(0, w * h, (4, max_pts)).astype(np.int32)
-        out_per = (3 * ((max_pts + 3) // 4) * 4 + 15) & ~15
+        out_per = emu.emu_colour_bgr_per(max_pts)                  # the size svslam_dense_cloud_bgr_batch allocates per job
+        assert out_per == (3 * ((max_pts + 3) // 4) * 4 + 15) & ~15
         out = np.full((4, out_per), 0xEE, np.uint8)
         emu.emu_colour_gather(4, _p(counts), _p(plane_of), _p(pix), max_pts, _p(planes), w * h * 3, _p(out), out_per)
         for j in range(4):

@@ -3,32 +3,29 @@ restatement: the kernel's tiling, chunk dealing, quarter scans, merge, texture w
 Not a replacement for tests/test_gpu_stereo_bm.py (the compiler, the ISA and the launch are not in it); it is what makes a one-line
 change of the kernel's logic visible on a machine without a device."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import ref_stereo_bm as rbm
+from test_gpu_stereo_bm import EARLY_OUT, STRIPS
 from test_ref_stereo_bm import band_pair, bw_pair, hand_pairs, texture_ramp_pair, tie_pair, uniqueness_ramp_pair
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "stereovision-slam_amd", "csrc")
-EMU = os.path.join(ROOT, "tests", "cpp", "bm_host_emu")
+
+class BmPlan(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("x0", "x1", "y0", "y1", "th", "tiles", "strips")] + [("lds", C.c_size_t)]
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    d = tmp_path_factory.mktemp("bm_host_emu")
-    src = open(os.path.join(CSRC, "k_stereo_bm.h")).read()
-    cut = src.index("// ---- the cloud")                                    # the matcher only
-    lds = "    extern __shared__ unsigned int bm_lds[];\n"
-    assert src.count(lds) == 1
-    open(str(d / "k_stereo_bm.h"), "w").write(src[:cut].replace(lds, "    unsigned int *bm_lds = g_lds;\n"))
-    so = str(d / "libbm_host_emu.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-I", str(d), "-I", EMU, os.path.join(EMU, "emu.cpp"), "-o", so])
-    lib = C.CDLL(so)
+def lib(svs):
+    L = C.CDLL(svs._build.build_emu("bm"))
+    L.emu_bm_plan.restype = BmPlan
+    L.emu_bm_lds_bytes.restype = C.c_longlong
+    return L
 
+
+@pytest.fixture(scope="module")
+def emu(lib):
     def run(left, right, th=0, num_disparities=128, block_size=15, pre_filter_cap=31, texture_threshold=10, uniqueness_ratio=15):
         left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
         h, w = left.shape
@@ -84,3 +81,25 @@ def test_kernel_source_on_the_host_equals_the_restatement(svs, emu):
         if not np.array_equal(got, ref):
             bad.append((name, int((got != ref).sum())))
     assert not bad, bad
+
+
+# tiles x strips x njobs of the STRIPS rows, by hand from the comment above them (test_gpu_stereo_bm.py): 8 x 11 x 12, 8 x 22 x 6,
+# 3 x 3 x 114, 3 x 5 x 69, 2 x 2 x 256 and, where even strips of 4 stay far below 1024 workgroups, 2 x 8 x 2
+WORKGROUPS = [1056, 1056, 1026, 1035, 1024, 32]
+
+
+def test_plan_is_the_strip_rule_of_the_device_tests(lib):
+    """bm_plan, the function svslam_stereo_bm_strip_rows and the launch take their numbers from"""
+    def plan(w, h, njobs, nd, bs):
+        p = lib.emu_bm_plan(w, h, njobs, nd, bs)
+        return {k: getattr(p, k) for k, _ in BmPlan._fields_}
+    assert [th for *_, th in STRIPS] == [16, 8, 16, 8, 16, 4]
+    for (w, h, nd, bs, njobs, th), wgs in zip(STRIPS, WORKGROUPS):
+        p, r = plan(w, h, njobs, nd, bs), bs // 2
+        assert p["th"] == th and p["tiles"] * p["strips"] * njobs == wgs, (w, h, nd, bs, njobs, p)
+        assert (p["x0"], p["x1"], p["y0"], p["y1"]) == (nd - 1 + r, w - r, r, h - r)
+        assert p["tiles"] == -(-(p["x1"] - p["x0"]) // 64) and p["strips"] == -(-(p["y1"] - p["y0"]) // th)
+        assert p["lds"] == lib.emu_bm_lds_bytes(nd, bs, th) and p["lds"] <= 160 * 1024
+    for w, h, nd, bs in EARLY_OUT:
+        p = plan(w, h, 2, nd, bs)
+        assert p["th"] == 0 and p["x0"] >= p["x1"] and p["y0"] >= p["y1"], (w, h, nd, bs, p)      # k_bm_fill's window is empty
