@@ -388,6 +388,45 @@ int svslam_pose_graph_batch(svslam_ctx *ctx, int njobs, svslam_pg_job *jobs,
                             int total_pts, const int *pt_anchor /* local vertex or -1 */, double *pts /* in/out */,
                             int iters);
 
+/* ---- local fusion: a verified loop corrects the active window ----------------------
+ * The arithmetic of LoopClosure::LocalFusion (src/loopclosure.cpp:439-526), one job per closed loop; `cur` is the keyframe that
+ * closed it, T_corr its corrected pose (svslam_loop_job::T_corr).  The landmark replacement that follows in the reference
+ * (:530-573) is map bookkeeping and stays with the caller.
+ *  1. corrected table (:451-467): row i < nkf is window keyframe i, corrected[i] = (T_i T_cur^-1) T_corr in that association;
+ *     corrected[cur] = T_corr.  cur >= 0 is its index in the window; cur = -1: it has left the window, T_cur is given in the job and
+ *     the table has one more row, number nkf, for it.
+ *  2. landmarks (:470-503): landmark g of the call has the observations obs_kf[obs_ptr[g] .. obs_ptr[g + 1]) in list order; an entry is
+ *     the table row of the observation's keyframe (a right-image observation counts, its frame is the keyframe), or -1 where the
+ *     feature no longer names a live landmark or its frame has no row.  The FIRST entry k >= 0 moves the landmark:
+ *     p' = corrected[k]^-1 (T_k p) with the old T_k; pt_kf[g] = k.  No such entry: the position is kept, pt_kf[g] = -1 and the job's
+ *     n_unanchored counts it (the reference asserts and dereferences null there: declared deviation).
+ *  3. last frame (:506-526): last >= 0 is its index in the window and T_last comes back as that row of the table; last = -1: it is no
+ *     active keyframe and T_last becomes (T_last T_cur^-1) T_corr.
+ * poses comes back as rows 0 .. nkf - 1 of the table (:511-519 writes the active keyframes only: an inactive cur is not written
+ * anywhere).  All in f64 with the SE(3) operations of svslam_pose_graph_batch, no contraction: a job's result depends on nothing
+ * but its inputs, and two calls give the same bits.
+ * Errors, nothing written and nothing launched: a null array whose count is not 0; a negative count; jobs whose kf / pt ranges
+ * leave the arrays, do not ascend from job to job or overlap (gaps are allowed and come back untouched); an obs_ptr that descends or
+ * leaves obs_kf; an obs_kf outside [-1, nkf] (nkf only with cur = -1); cur or last outside [-1, nkf); a quaternion (window poses,
+ * T_corr, T_cur with cur = -1, T_last with last = -1) whose squared norm is further than 2e-6 from 1; no memory for the call's
+ * buffer (allocated on demand and kept; njobs is not bounded by max_jobs).  njobs == 0 is success.                             */
+typedef struct svslam_lf_job {
+    int kf_ofs, nkf;        /* the active window */
+    int pt_ofs, npt;        /* the active landmarks; their observation lists are obs_ptr[pt_ofs .. pt_ofs + npt] */
+    int cur;                /* index of cur in the window, or -1 */
+    int last;               /* index of the frontend's last frame in the window, or -1 */
+    double T_cur[7];        /* read when cur == -1 */
+    double T_corr[7];
+    double T_last[7];       /* in (read when last == -1) / out */
+    int n_unanchored;       /* out */
+    int reserved;
+} svslam_lf_job;
+
+int svslam_local_fusion_batch(svslam_ctx *ctx, int njobs, svslam_lf_job *jobs,
+                              int total_kf, double *poses /* in/out, 7 each */,
+                              int total_pts, double *pts /* in/out */, const int *obs_ptr /* total_pts + 1 */,
+                              int total_obs, const int *obs_kf, int *pt_kf /* out, total_pts */);
+
 /* ---- loop verification: Hamming match, PnP RANSAC, loop gates ---------------------
  * Replaces LoopClosure::KeypointMatchWithLoopCandid and LoopClosure::CalculatePose (src/loopclosure.cpp:286-437, called at :831-862).
  * One job is one keyframe pair of one stream: nc descriptors of the candidate (older) keyframe with the landmark of each one's
@@ -826,7 +865,8 @@ int svslam_sync(svslam_ctx *ctx);
  * 14 loop_verify (units = jobs; appended after 13, nothing moved), 15 brief (units = points; appended after 14, nothing moved),
  * 16 loop_candidates (units = rows compared, summed over the jobs; appended after 15, nothing moved),
  * 17 global_desc (units = jobs; appended after 16, nothing moved),
- * 18 colour (the conversion kernel of svslam_pyramid_bgr_batch; units = images; appended after 17, nothing moved).
+ * 18 colour (the conversion kernel of svslam_pyramid_bgr_batch; units = images; appended after 17, nothing moved),
+ * 19 local_fusion (units = jobs; appended after 18, nothing moved).
  * Development families follow and are NOT stable numbers: with stereo_bm taking 6, the
  * per-kernel split moved from 6-9 to 7-10 and the local-BA solver interval from 10 to 11.
  * A caller that passed those raw numbers must move with them (Python addresses them by name). */

@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "svslam_pyramid_batch", "svslam_pyramid_decimate_batch", "svslam_set_source_size", "svslam_set_low_latency", "svslam_set_pose_only_xtol", "svslam_get_pose_only_xtol", "svslam_pyramid_read",
     "svslam_pyramid_read_padded", "svslam_stereo_bm_batch", "svslam_stereo_bm_strip_rows", "svslam_dense_cloud_batch", "svslam_cloud_sor_batch", "svslam_cloud_voxel_grid", "svslam_debug_cloud_sor_climbs",
     "svslam_colour_reserve", "svslam_pyramid_bgr_batch", "svslam_colour_read", "svslam_dense_cloud_bgr_batch", "svslam_lk_batch", "svslam_gftt_batch", "svslam_gftt_eigmap", "svslam_triangulate_batch",
-    "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect", "svslam_pose_graph_batch", "svslam_loop_verify_batch", "svslam_brief_describe_batch", "svslam_brief_default_pattern",
+    "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect", "svslam_pose_graph_batch", "svslam_local_fusion_batch", "svslam_loop_verify_batch", "svslam_brief_describe_batch", "svslam_brief_default_pattern",
     "svslam_loopdb_configure", "svslam_loopdb_append_batch", "svslam_loop_candidates_batch", "svslam_loopdb_count", "svslam_loopdb_read",
     "svslam_gdesc_configure", "svslam_gdesc_dim", "svslam_gdesc_describe_batch", "svslam_gdesc_mobilenet_v2",
     "svslam_track_batch", "svslam_rtrack_batch", "svslam_rtrack_upload",
@@ -42,8 +42,8 @@ KERNEL_FAMILIES = {"ba_solve": 11}
 CLOUD_FAMILIES = {"cloud_filter": 12}      # the outlier removal and the voxel grid of the dense program (units = points); appended, nothing renumbered
 # svslam_pose_graph_batch, svslam_loop_verify_batch (units = jobs), svslam_brief_describe_batch (units = points); appended after 12,
 # 13 and 14, nothing renumbered; svslam_loop_candidates_batch (units = rows compared) appended after 15
-# svslam_gdesc_describe_batch (units = jobs) appended after 16
-LOOP_FAMILIES = {"pose_graph": 13, "loop_verify": 14, "brief": 15, "loop_candidates": 16, "global_desc": 17}
+# svslam_gdesc_describe_batch (units = jobs) appended after 16; svslam_local_fusion_batch (units = jobs) appended after 18 (colour)
+LOOP_FAMILIES = {"pose_graph": 13, "loop_verify": 14, "brief": 15, "loop_candidates": 16, "global_desc": 17, "local_fusion": 19}
 # svslam_pyramid_bgr_batch's conversion kernel (units = images), appended after 17; a dictionary of its own: the dense program's, not the per-frame loop's
 COLOUR_FAMILIES = {"colour": 18}
 # the HIP kernel(s) behind each timing family at the batch operating point (what a rocprofv3 --kernel-trace --stats row is named)
@@ -51,7 +51,7 @@ FAMILY_KERNELS = {"pyramid": ["k_pyr_fused"], "lk": ["k_lk"], "gftt": ["k_gftt_e
                   "pose_only": ["k_pose_only"], "local_ba": ["k_dmap_ba_gather", "k_ba_build", "k_local_ba_t", "k_dmap_ba_scatter"],
                   "ba_solve": ["k_local_ba_t"], "stereo_bm": ["k_bm_fill", "k_stereo_bm", "k_dense_cloud"],
                   "cloud_filter": ["k_cf_keys", "k_cf_gather", "k_cf_knn", "k_vg_keys", "k_vg_heads", "k_vg_starts", "k_vg_reduce"],
-                  "pose_graph": ["k_pose_graph"], "loop_verify": ["k_loop_verify"], "brief": ["k_brief_filter", "k_brief_describe"],
+                  "pose_graph": ["k_pose_graph"], "local_fusion": ["k_local_fusion"], "loop_verify": ["k_loop_verify"], "brief": ["k_brief_filter", "k_brief_describe"],
                   "loop_candidates": ["k_lc_candidates"],
                   "colour": ["k_bgr_prepare"],
                   "global_desc": ["k_gd_prep", "k_gd_conv3", "k_gd_dw3", "k_gd_pw_mfma", "k_gd_pool"]}
@@ -100,6 +100,12 @@ class PgJob(C.Structure):
     _fields_ = [("kf_ofs", C.c_int), ("nkf", C.c_int), ("edge_ofs", C.c_int), ("nedge", C.c_int), ("pt_ofs", C.c_int),
                 ("npt", C.c_int), ("iters_done", C.c_int), ("n_trials", C.c_int), ("chi2_before", C.c_double),
                 ("chi2_after", C.c_double)]
+
+
+class LfJob(C.Structure):
+    _fields_ = [("kf_ofs", C.c_int), ("nkf", C.c_int), ("pt_ofs", C.c_int), ("npt", C.c_int), ("cur", C.c_int), ("last", C.c_int),
+                ("T_cur", C.c_double * 7), ("T_corr", C.c_double * 7), ("T_last", C.c_double * 7), ("n_unanchored", C.c_int),
+                ("reserved", C.c_int)]
 
 
 class LoopJob(C.Structure):
@@ -762,6 +768,43 @@ class Context:
                                                  int(iters)), "pose_graph")
         return [dict(poses=P[j.kf_ofs:j.kf_ofs + j.nkf].copy(), pts=X[j.pt_ofs:j.pt_ofs + j.npt].copy(), iters=j.iters_done,
                      trials=j.n_trials, chi2_before=j.chi2_before, chi2_after=j.chi2_after) for j in arr]
+
+    # ---- local fusion after a closed loop ---------------------------------------
+    def local_fusion(self, jobs):
+        """steps 1-3 of LoopClosure::LocalFusion for every job in one call (svslam_local_fusion_batch).
+        jobs: list of dicts with poses[n,7] (the active window), cur (index in the window, or -1 with T_cur[7]), T_corr[7],
+        last (index in the window, or -1 with T_last[7]), pts[m,3], obs_ptr[m+1] and obs_kf[obs_ptr[m]] (per observation in list
+        order the row of its keyframe in the corrected table: window index, n for a cur outside the window, -1 for none).
+        returns a list of dicts: poses, T_last, pts, pt_kf (the row a landmark moved with, or -1), n_unanchored."""
+        n = len(jobs)
+        arr = (LfJob * max(n, 1))()
+        P, X, OP, OK = [], [], [np.zeros(1, np.int32)], []
+        ko = po = oo = 0
+        for i, job in enumerate(jobs):
+            poses = np.ascontiguousarray(job["poses"], np.float64).reshape(-1, 7)
+            pts = job.get("pts")
+            pts = np.zeros((0, 3)) if pts is None else np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+            ptr = job.get("obs_ptr")
+            ptr = np.zeros(1, np.int64) if ptr is None else np.asarray(ptr, np.int64).reshape(-1)
+            okf = job.get("obs_kf")
+            okf = np.zeros(0, np.int32) if okf is None else np.ascontiguousarray(okf, np.int32).reshape(-1)
+            if len(ptr) != len(pts) + 1 or ptr[0] != 0 or ptr[-1] != len(okf):
+                raise ValueError("local_fusion: job %d: obs_ptr does not index %d points and %d observations" % (i, len(pts), len(okf)))
+            cur, last = int(job["cur"]), int(job["last"])
+            arr[i].kf_ofs, arr[i].nkf, arr[i].pt_ofs, arr[i].npt, arr[i].cur, arr[i].last = ko, len(poses), po, len(pts), cur, last
+            arr[i].T_corr = (C.c_double * 7)(*_d(job["T_corr"]).reshape(7))
+            if cur < 0:
+                arr[i].T_cur = (C.c_double * 7)(*_d(job["T_cur"]).reshape(7))
+            if last < 0:
+                arr[i].T_last = (C.c_double * 7)(*_d(job["T_last"]).reshape(7))
+            P.append(poses); X.append(pts); OP.append((ptr[1:] + oo).astype(np.int32)); OK.append(okf)
+            ko += len(poses); po += len(pts); oo += len(okf)
+        cat = lambda v, shape, dt: np.ascontiguousarray(np.concatenate(v)) if v else np.zeros(shape, dt)
+        P = cat(P, (0, 7), np.float64); X = cat(X, (0, 3), np.float64); OP = cat(OP, 1, np.int32); OK = cat(OK, 0, np.int32)
+        K = np.full(po, -1, np.int32)
+        self._chk(self.L.svslam_local_fusion_batch(self.h, n, arr, ko, _p(P), po, _p(X), _p(OP), oo, _p(OK), _p(K)), "local_fusion")
+        return [dict(poses=P[j.kf_ofs:j.kf_ofs + j.nkf].copy(), T_last=np.array(j.T_last), pts=X[j.pt_ofs:j.pt_ofs + j.npt].copy(),
+                     pt_kf=K[j.pt_ofs:j.pt_ofs + j.npt].copy(), n_unanchored=j.n_unanchored) for j in arr[:n]]
 
     # ---- loop verification -----------------------------------------------------
     def loop_verify(self, jobs, cam, ext_l, **params):

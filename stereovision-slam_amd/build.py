@@ -5,8 +5,8 @@
   lib/libsvslam_pipeline.so C++ host pipeline (Frontend/Backend/Map mirror of the
                             reference) bound to libsvslam_hip.so
   lib/lib<name>_host_emu.so a kernel header of csrc/ compiled for the host by tests/cpp/<name>_host_emu/emu.cpp, one per
-                            entry of EMUS (lv, pg, brief, lc, gd: k_loop_verify.h, k_pose_graph.h, k_brief.h,
-                            k_loop_candidates.h, k_global_desc.h; bm, cf, colour: k_stereo_bm.h, k_cloud_filter.h,
+                            entry of EMUS (lv, pg, lf, brief, lc, gd: k_loop_verify.h, k_pose_graph.h, k_local_fusion.h,
+                            k_brief.h, k_loop_candidates.h, k_global_desc.h; bm, cf, colour: k_stereo_bm.h, k_cloud_filter.h,
                             k_colour.h).  The build fails here, not in a test, when a kernel file stops being plain
                             C++ between the HIP qualifiers; the tests load the same libraries through build_emu
 
@@ -109,6 +109,7 @@ _C, _SHIM = "stereovision-slam_amd/csrc/", "tests/cpp/hip_on_host.h"
 EMUS = {
     "lv": ([_C + "k_loop_verify.h", _C + "k_pose_graph.h"], []),
     "pg": ([_C + "k_pose_graph.h"], []),
+    "lf": ([_C + "k_local_fusion.h", _C + "k_pose_graph.h"], []),
     "brief": ([_C + "k_brief.h"], []),
     "lc": ([_C + "k_loop_candidates.h"], []),
     "gd": ([_C + "k_global_desc.h"], []),

@@ -1,5 +1,5 @@
-// api_loop.h — included by svslam_hip.hip.  Entry points: svslam_pose_graph_batch, svslam_loop_verify_batch, svslam_brief_*,
-// svslam_loopdb_*, svslam_loop_candidates_batch, svslam_gdesc_*.  Owns of svslam_ctx: pg, lv, br, lc, gd.
+// api_loop.h — included by svslam_hip.hip.  Entry points: svslam_pose_graph_batch, svslam_loop_verify_batch, svslam_local_fusion_batch,
+// svslam_brief_*, svslam_loopdb_*, svslam_loop_candidates_batch, svslam_gdesc_*.  Owns of svslam_ctx: pg, lv, lf, br, lc, gd.
 
 extern "C" {
 
@@ -100,6 +100,37 @@ int svslam_loop_verify_batch(svslam_ctx *c, int njobs, svslam_loop_job *jobs, co
         memcpy(match_c, Hb.m_c, 4 * (size_t)total_c); memcpy(match_q, Hb.m_q, 4 * (size_t)total_c); memcpy(match_dist, Hb.m_d, 4 * (size_t)total_c);
         memcpy(match_inlier, Hb.m_inl, (size_t)total_c);
     }
+    return 0;
+}
+
+// ------------------------------------------------------------------ local fusion after a closed loop
+int svslam_local_fusion_batch(svslam_ctx *c, int njobs, svslam_lf_job *jobs, int total_kf, double *poses, int total_pts, double *pts,
+                              const int *obs_ptr, int total_obs, const int *obs_kf, int *pt_kf)
+{
+    if (!c) return -1;
+    std::vector<LfIn> in((size_t)(njobs > 0 && jobs ? njobs : 0));
+    for (size_t j = 0; j < in.size(); ++j) {
+        svslam_lf_job &s = jobs[j];
+        in[j] = LfIn{ s.kf_ofs, s.nkf, s.pt_ofs, s.npt, s.cur, s.last, s.T_cur, s.T_corr, s.T_last };
+    }
+    const char *why = lf_plan(njobs, jobs ? in.data() : nullptr, total_kf, poses, total_pts, pts, obs_ptr, total_obs, obs_kf, pt_kf);
+    if (why) return fail(c, "local_fusion: %s", why);
+    if (njobs == 0) return 0;
+    if (arena_busy(c)) return -1;
+    LfSizes Z;
+    (void)lf_layout(Z, njobs, total_kf, total_pts, total_obs, nullptr);          // sizes
+    if (c->lf.reserve(c, "local_fusion", Z.bytes, Z.bytes / 4, Z.bytes)) return -1;
+    const LfBuf Hb = lf_layout(Z, njobs, total_kf, total_pts, total_obs, c->lf.h.data());
+    const LfBuf Db = lf_layout(Z, njobs, total_kf, total_pts, total_obs, c->lf.d);
+    lf_fill(Z, Hb, njobs, in.data(), total_kf, poses, total_pts, pts, obs_ptr, total_obs, obs_kf);
+    HIPCHK(c, hipMemcpyAsync(c->lf.d, c->lf.h.data(), Z.bytes, hipMemcpyHostToDevice, c->stream));
+    tm_begin(c, FAM_LF, njobs);
+    hipLaunchKernelGGL(k_local_fusion, dim3(njobs), dim3(LF_THREADS), 0, c->stream, Db);
+    tm_end(c);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->lf.h.data(), c->lf.d, Z.result_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (d2h_sync(c, 0, 0)) return -1;
+    for (int j = 0; j < njobs; ++j) lf_copy_out(Hb, j, poses, pts, pt_kf, jobs[j].T_last, &jobs[j].n_unanchored);
     return 0;
 }
 

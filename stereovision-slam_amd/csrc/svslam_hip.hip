@@ -50,6 +50,7 @@ typedef enum { ncclDouble = 8 } ncclDataType_t;
 #include "k_cloud_filter.h"
 #include "k_pose_graph.h"
 #include "k_loop_verify.h"
+#include "k_local_fusion.h"
 #include "k_brief.h"
 #include "k_loop_candidates.h"
 #include "k_global_desc.h"
@@ -72,6 +73,7 @@ enum { FAM_PYR = 0, FAM_LK, FAM_GFTT, FAM_TRI, FAM_POSE, FAM_BA,
        FAM_LC,         // 16: "loop_candidates", svslam_loop_candidates_batch (units = rows compared); appended, nothing moved
        FAM_GD,         // 17: "global_desc", svslam_gdesc_describe_batch (units = jobs); appended, nothing moved
        FAM_COL,        // 18: "colour", k_bgr_prepare of svslam_pyramid_bgr_batch (units = images); appended, nothing moved
+       FAM_LF,         // 19: "local_fusion", svslam_local_fusion_batch (units = jobs); appended, nothing moved
        FAM_COUNT };
 
 struct Timing {
@@ -139,6 +141,8 @@ struct svslam_ctx {
     DevBuf lv;
     // descriptors (svslam_brief_describe_batch): the same arrangement
     DevBuf br;
+    // local fusion (svslam_local_fusion_batch): the same arrangement
+    DevBuf lf;
     // loop candidates: the resident store of normalised global descriptors (S on the device, H its bookkeeping) and a call's staging
     struct : DevBuf { LcStore S = {}; LcHost H; } lc;
     // global descriptor (svslam_gdesc_*): the configured network, its parameters and resize tables on the device, the workspace of a

@@ -122,6 +122,10 @@ public:
                    const int *eb, const double *meas, int total_pts, const int *anchor, double *pts, int iters)
     { return svslam_pose_graph_batch(ctx_, n, jobs, total_kf, poses, fixed, total_edges, ea, eb, meas, total_pts, anchor, pts, iters); }
 
+    int local_fusion(int n, svslam_lf_job *jobs, int total_kf, double *poses, int total_pts, double *pts, const int *obs_ptr, int total_obs,
+                     const int *obs_kf, int *pt_kf)
+    { return svslam_local_fusion_batch(ctx_, n, jobs, total_kf, poses, total_pts, pts, obs_ptr, total_obs, obs_kf, pt_kf); }
+
     int loop_verify(int n, svslam_loop_job *jobs, const svslam_loop_params *prm, int total_c, const uint8_t *desc_c, const double *xyz_c,
                     const uint8_t *has_xyz, int total_q, const uint8_t *desc_q, const float *uv_q, int *mc, int *mq, int *md, uint8_t *mi)
     { return svslam_loop_verify_batch(ctx_, n, jobs, prm, total_c, desc_c, xyz_c, has_xyz, total_q, desc_q, uv_q, mc, mq, md, mi); }

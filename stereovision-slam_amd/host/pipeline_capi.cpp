@@ -174,6 +174,16 @@ extern "C" int svs_pipe_loopdb_configure(void *p, int capacity, int dim)
 }
 extern "C" int svs_pipe_detect_loops(void *p, const float *vecs, const svs_loop_detect_params *dp, const void *loop_params, svs_loop_detection *results)
 {
+    return svs_pipe_detect_loops_fused(p, vecs, dp, loop_params, 0, results, nullptr);
+}
+static void put_stats(svs_fusion_stats &o, bool fused, const svs::Pipeline<SVS_PIPE_KERNELS>::FusionStats &S)
+{
+    o.fused = fused ? 1 : 0; o.nkf = S.nkf; o.npt = S.npt; o.n_unanchored = S.n_unanchored; o.pairs = S.pairs; o.merged = S.merged;
+    o.revived = S.revived; o.repointed = S.repointed; o.same_deleted = S.same_deleted; o.reserved = 0;
+}
+extern "C" int svs_pipe_detect_loops_fused(void *p, const float *vecs, const svs_loop_detect_params *dp, const void *loop_params, int local_fusion,
+                                           svs_loop_detection *results, svs_fusion_stats *fusion_or_null)
+{
     typedef svs::Pipeline<SVS_PIPE_KERNELS> Pipe;
     PipeHandle *h = static_cast<PipeHandle *>(p);
     if (!dp || !loop_params || !results) { g_err = "svs_pipe_detect_loops: null argument"; return -1; }     // vecs == NULL: the configured network
@@ -182,8 +192,11 @@ extern "C" int svs_pipe_detect_loops(void *p, const float *vecs, const svs_loop_
         P.cand.weak = dp->weak; P.cand.strong = dp->strong; P.cand.max_num_weak = dp->max_num_weak; P.cand.min_gap = dp->min_gap;
         P.verify = *static_cast<const svslam_loop_params *>(loop_params);
         P.keyframes_to_ignore_after_loop = dp->keyframes_to_ignore_after_loop;
+        P.local_fusion = local_fusion != 0;
         std::vector<Pipe::LoopDetection> ds;
-        if (!h->pipe->DetectLoops(vecs, P, &ds)) { g_err = h->pipe->last_error(); return -1; }
+        // a refusal of the fusion comes after the detection has taken effect: ds is filled then, and so are the results
+        const bool ok = h->pipe->DetectLoops(vecs, P, &ds);
+        if (!ok) { g_err = h->pipe->last_error(); if (ds.empty()) return -1; }
         for (size_t s = 0; s < ds.size(); ++s) {
             const Pipe::LoopDetection &D = ds[s];
             svs_loop_detection &o = results[s];
@@ -196,8 +209,9 @@ extern "C" int svs_pipe_detect_loops(void *p, const float *vecs, const svs_loop_
             o.loop.status = D.verified ? R.status : -1; o.loop.n_matches = R.n_matches; o.loop.n_points = R.n_points; o.loop.n_inliers = R.n_inliers;
             o.loop.need_correction = R.need_correction ? 1 : 0;
             std::memcpy(o.loop.T_corr, R.T_corr.v, 56); std::memcpy(o.loop.T_rel, R.T_rel.v, 56); o.loop.d = R.d;
+            if (fusion_or_null) put_stats(fusion_or_null[s], D.fused, D.fusion);
         }
-        return 0;
+        return ok ? 0 : -1;
     } catch (const std::exception &e) {
         g_err = e.what();
         return -1;
@@ -256,3 +270,54 @@ extern "C" long long svs_pipe_loopdb_ids(void *p, int stream, int *ids, long lon
 }
 extern "C" long long svs_pipe_last_closed_keyframe(void *p, int stream) { return static_cast<PipeHandle *>(p)->pipe->LastClosedKeyframe(stream); }
 extern "C" void *svs_pipe_backend_ctx(void *p) { return static_cast<PipeHandle *>(p)->kernels->backend_ctx(); }
+// LocalFusion (product build only: the CPU twins' providers have no local_fusion)
+extern "C" int svs_pipe_local_fusion(void *p, int njobs, const svs_fusion_job *jobs, const int *pairs2, svs_fusion_stats *stats_or_null)
+{
+    typedef svs::Pipeline<SVS_PIPE_KERNELS> Pipe;
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    if (njobs < 0 || (njobs > 0 && !jobs)) { g_err = "svs_pipe_local_fusion: null argument"; return -1; }
+    try {
+        std::vector<Pipe::FusionJob> js((size_t)njobs);
+        for (int i = 0; i < njobs; ++i) {
+            const svs_fusion_job &j = jobs[i];
+            if (j.npairs < 0 || j.pair_ofs < 0 || (j.npairs > 0 && !pairs2)) { g_err = "svs_pipe_local_fusion: a job's pairs are null or negative"; return -1; }
+            js[(size_t)i].stream = j.stream; js[(size_t)i].kf_id = (long)j.kf_id; js[(size_t)i].cand_kf_id = (long)j.cand_kf_id; js[(size_t)i].T_corr = svs::SE3(j.T_corr);
+            for (int k = 0; k < j.npairs; ++k) js[(size_t)i].pairs.emplace_back(pairs2[2 * (j.pair_ofs + k)], pairs2[2 * (j.pair_ofs + k) + 1]);
+        }
+        std::vector<Pipe::FusionStats> st;
+        if (!h->pipe->LocalFusion(js, &st)) { g_err = h->pipe->last_error(); return -1; }
+        if (stats_or_null) for (size_t i = 0; i < st.size(); ++i) put_stats(stats_or_null[i], true, st[i]);
+        return 0;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+extern "C" long long svs_pipe_all_landmarks(void *p, int stream, double *out7, long long cap)
+{
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    if (stream < 0 || stream >= h->pipe->nstreams()) { g_err = "svs_pipe_all_landmarks: no such stream"; return -1; }
+    try {
+        h->pipe->Flush();
+        const std::vector<svs::LandmarkRecord> all = h->pipe->AllLandmarks(stream);
+        const long long n = (long long)all.size();
+        if (out7 && cap >= n)
+            for (long long i = 0; i < n; ++i) {
+                const svs::LandmarkRecord &r = all[(size_t)i];
+                double *o = out7 + 7 * i;
+                o[0] = (double)r.id; o[1] = r.pos[0]; o[2] = r.pos[1]; o[3] = r.pos[2]; o[4] = r.observed_times; o[5] = r.active ? 1.0 : 0.0; o[6] = (double)r.anchor_kf;
+            }
+        return n;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+extern "C" long long svs_pipe_last_frame(void *p, int stream, double *pose7)
+{
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    if (stream < 0 || stream >= h->pipe->nstreams() || !h->pipe->stream(stream).last) { g_err = "svs_pipe_last_frame: no such stream, or it has seen no frame"; return -2; }
+    const svs::Frame *f = h->pipe->stream(stream).last;
+    if (pose7) std::memcpy(pose7, f->pose.v, 56);
+    return f->is_keyframe ? (long long)f->keyframe_id : -1;
+}

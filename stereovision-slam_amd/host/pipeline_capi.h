@@ -124,8 +124,8 @@ int svs_pipe_loopdb_configure(void *p, int capacity, int dim);
  * call).  vecs: [nstreams][dim] global descriptors, the rows of streams without a new keyframe are not read.  loop_params:
  * svslam_loop_params (cam and ext_l are filled in by the pipeline).  results: [nstreams]; cand_status and loop.status are -1 where that
  * stage did not run.  The matches of a verified stream: svs_pipe_loop_matches.  -1 (svs_pipe_last_error, nothing done): device_map =
- * 1, a store that was not configured, a new keyframe that was never described, a full stream, a kernel's refusal.  LocalFusion is the
- * caller's.  vecs == NULL: the vectors come from the network svs_pipe_gdesc_configure set, computed here for the keyframes this call
+ * 1, a store that was not configured, a new keyframe that was never described, a full stream, a kernel's refusal.  LocalFusion is
+ * not done here (svs_pipe_detect_loops_fused, or svs_pipe_local_fusion with the result).  vecs == NULL: the vectors come from the network svs_pipe_gdesc_configure set, computed here for the keyframes this call
  * handles; refused when no network is configured or when the store's dim is not the network's. */
 typedef struct svs_loop_detect_params { float weak, strong; int max_num_weak, min_gap; long long keyframes_to_ignore_after_loop; } svs_loop_detect_params;
 typedef struct svs_loop_detection {
@@ -135,6 +135,33 @@ typedef struct svs_loop_detection {
     svs_loop_result loop;
 } svs_loop_detection;
 int svs_pipe_detect_loops(void *p, const float *vecs, const svs_loop_detect_params *dp, const void *loop_params, svs_loop_detection *results);
+/* svs_pipe_detect_loops that, with local_fusion != 0, ends with LoopClosure::LocalFusion (src/loopclosure.cpp:439-582, as
+ * LoopClosureUpdate calls it: only where need_correction is set) for every stream whose pair was ACCEPTED, in one kernel call: its
+ * pairs are the match rows whose candidate feature had a landmark, mapped through desc_feat_indx.  fusion_or_null: [nstreams], fused = 1
+ * where it ran.  With local_fusion == 0 this IS svs_pipe_detect_loops; the structs of that call are unchanged.  -1 after the
+ * detection itself succeeded (a refusal of the fusion): the loop edges and the store are as svs_pipe_detect_loops leaves them, no
+ * map was fused, and results (and fusion_or_null, fused = 0) are filled as on success. */
+typedef struct svs_fusion_stats { int fused, nkf, npt, n_unanchored, pairs, merged, revived, repointed, same_deleted, reserved; } svs_fusion_stats;
+int svs_pipe_detect_loops_fused(void *p, const float *vecs, const svs_loop_detect_params *dp, const void *loop_params, int local_fusion,
+                                svs_loop_detection *results, svs_fusion_stats *fusion_or_null);
+/* LoopClosure::LocalFusion for njobs closed loops (at most one per stream) in one kernel call (svslam_local_fusion_batch), for a
+ * caller who verified the loop itself: the active window, the active landmarks and the frontend's last frame move with the
+ * corrected pose T_corr of keyframe kf_id; then, for every pair (feature index in the loop keyframe cand_kf_id, feature index in
+ * kf_id) in ascending order, the loop keyframe's landmark - brought back from the archive when it is dead - takes over the
+ * observations of the current feature's landmark, which is removed from the map.  pairs2: 2 ints per pair, a job's pairs start at
+ * pair_ofs.  stats_or_null: [njobs].  A local BA in flight is collected first; with resident tracking the stream's feature list is
+ * uploaded again.  -1 (svs_pipe_last_error, NOTHING changed for any job): device_map = 1, an unknown stream, two jobs on one
+ * stream, ids that are not keyframes, cand >= kf, a keyframe whose feature list was released (svs_pipe_keep_keyframe_features), an
+ * index out of range, a repeated pair, a T_corr that is no unit quaternion, resident tracking where the stream's last frame is not
+ * kf_id (its features are then held only by the kernel provider).  Product library only. */
+typedef struct svs_fusion_job { int stream, npairs; long long kf_id, cand_kf_id, pair_ofs; double T_corr[7]; } svs_fusion_job;
+int svs_pipe_local_fusion(void *p, int njobs, const svs_fusion_job *jobs, const int *pairs2, svs_fusion_stats *stats_or_null);
+/* Map::landmarks_ of a stream, read-only, id-ascending: 7 doubles each (id, x, y, z, observation counter, active flag, keyframe id of
+ * the anchor or -1); dead landmarks come from the archive (float positions, counter 0).  Returns their number (nothing written when
+ * cap is smaller or out7 is NULL), -1 for a bad stream. */
+long long svs_pipe_all_landmarks(void *p, int stream, double *out7, long long cap);
+/* the frontend's last frame of a stream: its pose, and its keyframe id or -1 when it is no keyframe; -2: a bad stream / no frame yet */
+long long svs_pipe_last_frame(void *p, int stream, double *pose7);
 /* The network behind the global image descriptor (svslam_gdesc_configure): layers is svslam_gd_layer [nlayers], params the
  * weights and biases in table order, prep_or_null svslam_gd_prep or NULL for the reference's call.  -1: the kernel's refusal, the
  * network configured before is kept.  svs_pipe_gdesc_dim: floats per descriptor, 0 while none is configured.  Product library only. */

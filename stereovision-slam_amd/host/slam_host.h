@@ -28,6 +28,7 @@
 #include <fstream>
 #include <functional>
 #include <iomanip>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -196,8 +197,67 @@ public:
     }
     MapPoint *point(long id)
     {
-        if (id < base_id_) return nullptr;           // covers id == -1 (no map point) and evicted ids below the window
+        if (id < base_id_) {                         // covers id == -1 (no map point) and evicted ids below the window
+            if (revived_.empty() || id < 0) return nullptr;
+            auto it = revived_.find(id);             // ... unless a loop brought one back (Revive): empty on a run without loops
+            return it == revived_.end() ? nullptr : it->second;
+        }
         return slots_[(size_t)(id - base_id_)];
+    }
+    // Map::RemoveLandmark (src/map.cpp:42-51): erased from landmarks_ and active_landmarks_, which destroys it.  The slot becomes
+    // null and the landmark is NOT archived (SaveOutputs writes landmarks_, which no longer has it); features keep the stale id,
+    // and point(id) == nullptr is their expired weak_ptr.  The object is recycled.
+    void RemoveLandmark(MapPoint *m)
+    {
+        if (!m) return;
+        if (m->active) { active_landmarks_.erase(std::remove(active_landmarks_.begin(), active_landmarks_.end(), m), active_landmarks_.end()); m->active = false; }
+        if (m->in_limbo) { limbo_.erase(std::remove(limbo_.begin(), limbo_.end(), m), limbo_.end()); m->in_limbo = false; }
+        Unslot(m);
+        m->observations.clear(); m->observed_times = 0;
+        free_.push_back(m);
+    }
+    // A dead landmark back from its 20-byte archive record, for LocalFusion: in the reference Map::landmarks_ still owns it, so the
+    // loop keyframe's feature can lock it.  Old id, the archived position widened to double (declared deviation: the reference
+    // still has the double; the error is at most half an f32 ulp), no observations, not active, the anchor rebuilt from the
+    // record's keyframe id (only the frame pointer of an anchor is ever dereferenced; its feature index is -1, which no real
+    // observation has, so RemoveObservation's `anchor == f` can never take it for one of the list).  The record is superseded: the id is listed
+    // once everywhere.  It waits in limbo like any unobserved landmark outside the window: observed again it leaves limbo, named
+    // by nothing it is archived again at the next keyframe.  nullptr: the id is live already, or found in no record (keep_archive
+    // off, or removed by an earlier fusion) - the reference's expired pointer.
+    MapPoint *Revive(long id)
+    {
+        if (id < 0 || id >= next_id_ || point(id)) return nullptr;
+        auto a = archive_.begin();
+        while (a != archive_.end() && (long)a->id != id) ++a;
+        if (a == archive_.end()) return nullptr;
+        MapPoint *m;
+        if (!free_.empty()) { m = free_.back(); free_.pop_back(); } else { pool_.emplace_back(); m = &pool_.back(); }
+        m->id = id; m->is_outlier = false; m->active = false; m->in_limbo = false; m->observed_times = 0; m->seen_stamp = -1; m->observations.clear();
+        for (int k = 0; k < 3; ++k) m->pos[k] = (double)a->pos[k];
+        m->has_anchor = a->anchor_kf >= 0 && (size_t)a->anchor_kf < keyframes_.size();
+        m->anchor = ObsRef{ m->has_anchor ? keyframes_[(size_t)a->anchor_kf] : nullptr, -1, true };
+        archive_.erase(a);
+        if (id >= base_id_) slots_[(size_t)(id - base_id_)] = m; else revived_[id] = m;
+        ToLimbo(m);
+        return m;
+    }
+    size_t num_revived_below_base() const { return revived_.size(); }
+    // Map::landmarks_ still holds the id: live, or dead with an archive record (in the reference a dead landmark is an ordinary
+    // member of landmarks_ that nothing observes).  Known, DropArchived and Revive scan the archive linearly, once per feature that
+    // names a dead landmark: fine for a call that runs once per closed loop, not for a per-frame path
+    bool Known(long id)
+    {
+        if (id < 0) return false;
+        if (point(id)) return true;
+        for (const ArchivedLandmark &a : archive_) if ((long)a.id == id) return true;
+        return false;
+    }
+    // Map::RemoveLandmark of a dead landmark: its archive record goes, nothing else refers to it.  False: no record of that id
+    bool DropArchived(long id)
+    {
+        for (auto a = archive_.begin(); a != archive_.end(); ++a)
+            if ((long)a->id == id) { archive_.erase(a); return true; }
+        return false;
     }
     size_t num_landmarks() const { return (size_t)next_id_; }                 // Map::landmarks_.size()
     size_t num_resident_landmarks() const { return pool_.size() - free_.size(); }
@@ -214,6 +274,7 @@ public:
         std::vector<LandmarkRecord> o;
         o.reserve(archive_.size() + slots_.size());
         for (const ArchivedLandmark &a : archive_) o.push_back(LandmarkRecord{ (long)a.id, { a.pos[0], a.pos[1], a.pos[2] }, 0, false, (long)a.anchor_kf });
+        for (const auto &r : revived_) { const MapPoint *m = r.second; o.push_back(LandmarkRecord{ m->id, { m->pos[0], m->pos[1], m->pos[2] }, m->observed_times, m->active, m->anchor_kf() }); }
         for (const MapPoint *m : slots_)
             if (m) o.push_back(LandmarkRecord{ m->id, { m->pos[0], m->pos[1], m->pos[2] }, m->observed_times, m->active, m->anchor_kf() });
         std::sort(o.begin(), o.end(), [](const LandmarkRecord &a, const LandmarkRecord &b) { return a.id < b.id; });
@@ -260,11 +321,12 @@ public:
                 if (!o.outlier && o.mp >= 0) { mp->anchor = mp->observations[i]; break; }
             }
     }
-    // every landmark SaveOutputs writes, archived ones first then the live ones: position and anchor keyframe (-1: none) out, the
+    // every landmark SaveOutputs writes, archived ones first, then the revived ones below the id window, then the live ones: position and anchor keyframe (-1: none) out, the
     // re-anchored positions back in the same order (Pipeline::PoseGraphOptimization)
     void CollectAnchored(std::vector<double> &pts, std::vector<int> &anchor) const
     {
         for (const ArchivedLandmark &a : archive_) { for (int k = 0; k < 3; ++k) pts.push_back((double)a.pos[k]); anchor.push_back(a.anchor_kf); }
+        for (const auto &r : revived_) { for (int k = 0; k < 3; ++k) pts.push_back(r.second->pos[k]); anchor.push_back((int)r.second->anchor_kf()); }
         for (const MapPoint *m : slots_) if (m) { for (int k = 0; k < 3; ++k) pts.push_back(m->pos[k]); anchor.push_back((int)m->anchor_kf()); }
     }
     // id -> archived float position of every dead landmark (Pipeline::VerifyLoops builds it once per call and stream; deque
@@ -277,6 +339,7 @@ public:
     void StoreAnchored(const double *pts)
     {
         for (ArchivedLandmark &a : archive_) { for (int k = 0; k < 3; ++k) a.pos[k] = (float)pts[k]; pts += 3; }
+        for (auto &r : revived_) { for (int k = 0; k < 3; ++k) r.second->pos[k] = pts[k]; pts += 3; }
         for (MapPoint *m : slots_) if (m) { for (int k = 0; k < 3; ++k) m->pos[k] = pts[k]; pts += 3; }
     }
     void CleanMap()                     // src/map.cpp:21-40
@@ -369,12 +432,14 @@ private:
     void Evict(MapPoint *m)
     {
         if (keep_archive_) archive_.push_back(ArchivedLandmark{ (uint32_t)m->id, { (float)m->pos[0], (float)m->pos[1], (float)m->pos[2] }, (int32_t)m->anchor_kf() });
-        slots_[(size_t)(m->id - base_id_)] = nullptr;
+        Unslot(m);
         free_.push_back(m);
     }
+    void Unslot(MapPoint *m) { if (m->id >= base_id_) slots_[(size_t)(m->id - base_id_)] = nullptr; else revived_.erase(m->id); }
     std::deque<MapPoint> pool_;               // MapPoint objects, recycled through free_
     std::vector<MapPoint *> free_, limbo_;    // limbo_: unobserved and outside the window, possibly still tracked
     std::vector<MapPoint *> slots_;           // id - base_id_ -> MapPoint (nullptr: evicted)
+    std::map<long, MapPoint *> revived_;      // revived landmarks whose id the window has slid past (Revive); empty unless a loop was fused
     long base_id_ = 0, next_id_ = 0;
     std::deque<ArchivedLandmark> archive_;    // (a deque: grows by 512-byte blocks, no doubling reallocation)
     bool keep_archive_ = true, keep_features_ = false;
@@ -694,8 +759,8 @@ public:
     // current keyframe's pixels come from kf->left; the candidate's landmarks from Map::point(id), or for a dead landmark from the
     // stream's archive (a float position: what the reference's cv::Point3f cast keeps anyway); mp == -1 or an id found in neither
     // place (keep_archive off) is has_xyz = 0, the reference's expired weak_ptr.  Every ACCEPTED result is recorded with
-    // AddLoopEdge(stream, kf, cand, T_rel).  LocalFusion (:439-582) is not done here: the result carries T_corr, need_correction and
-    // the matches (descriptor rows) for it.  A local BA in flight is collected first.  False (last_error(), nothing done):
+    // AddLoopEdge(stream, kf, cand, T_rel).  LocalFusion (:439-582) is not done here (Pipeline::LocalFusion, or DetectLoops with
+    // local_fusion): the result carries T_corr, need_correction and the matches (descriptor rows) for it.  A local BA in flight is collected first.  False (last_error(), nothing done):
     // device_map = 1, an unknown stream, ids that are not keyframes, cand >= kf, a desc_feat_indx entry out of range or repeated,
     // negative counts or null arrays, the provider's refusal.
     struct LoopQuery {
@@ -922,6 +987,129 @@ public:
         lc_last_closed_.assign((size_t)nstreams(), -1);
         return true;
     }
+    // LoopClosure::LocalFusion (src/loopclosure.cpp:439-582, as LoopClosureUpdate calls it at :625) for every job in ONE call of the
+    // kernel provider (DESIGN 15 has the rules).  A job names the keyframe that closed a loop, the loop keyframe, the corrected
+    // pose and KeypointMatches_ as pairs (feature index in cand->left, feature index in kf->left).  A local BA in flight is
+    // collected first; then, per job,
+    //   1-3  the provider moves the active window, the active landmarks and the last frame (local_fusion: the first-valid-observation
+    //        search runs there; the host hands it, per observation in list order, the row of its keyframe or -1)
+    //   4    the active keyframes take their corrected poses (an inactive kf is not written; relative_pose_pkf and relative_motion
+    //        are NOT refreshed: the stale edge is what a later pose-graph run distributes)
+    //   5    the pairs in ascending (ci, qi), each on the map as the pairs before it left it: the candidate's landmark, revived
+    //        from the archive when it is dead (Map::Revive), takes over the observations of the current feature's landmark, which
+    //        is removed (Map::RemoveLandmark; a dead one has no observation to move and only loses its archive record) - or, where
+    //        that one has expired, the feature is pointed at it.  The same landmark on
+    //        both sides is deleted (the reference's quirk).  The candidate's landmark is not made active.
+    // In resident mode the stream's feature list on the provider is uploaded again afterwards.
+    // False (last_error(), NOTHING changed for any job of the call): device_map = 1, an unknown stream, two jobs on one stream, ids
+    // that are not keyframes, cand >= kf, a keyframe whose feature list was released, a pair's index out of range, a repeated pair, a
+    // T_corr that is no unit quaternion, resident tracking where the last frame is not kf, the provider's refusal.
+    struct FusionJob { int stream = 0; long kf_id = -1, cand_kf_id = -1; SE3 T_corr; std::vector<std::pair<int, int>> pairs; };
+    struct FusionStats { int nkf = 0, npt = 0, n_unanchored = 0, pairs = 0, merged = 0, revived = 0, repointed = 0, same_deleted = 0; };
+    bool LocalFusion(const std::vector<FusionJob> &jobs, std::vector<FusionStats> *stats)
+    {
+        if (device_map()) return refuse("LocalFusion: with device_map = 1 the landmarks live on the device without anchors; not supported yet");
+        const int n = (int)jobs.size();
+        std::vector<std::vector<std::pair<int, int>>> order((size_t)n);
+        for (int j = 0; j < n; ++j) {
+            const FusionJob &F = jobs[(size_t)j];
+            if (F.stream < 0 || F.stream >= nstreams()) return refuse("LocalFusion: no such stream");
+            for (int i = 0; i < j; ++i) if (jobs[(size_t)i].stream == F.stream) return refuse("LocalFusion: two jobs on one stream");
+            const Stream &st = *streams_[F.stream];
+            const std::vector<Frame *> &kfs = st.map.keyframes_;
+            if (F.kf_id < 0 || F.kf_id >= (long)kfs.size() || F.cand_kf_id < 0 || F.cand_kf_id >= (long)kfs.size()) return refuse("LocalFusion: not a keyframe id of this stream");
+            if (F.cand_kf_id >= F.kf_id) return refuse("LocalFusion: the loop keyframe must be older than the keyframe");
+            const double *q = F.T_corr.v;
+            if (!(std::fabs(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] - 1.0) <= 2e-6)) return refuse("LocalFusion: the corrected pose's quaternion is not of unit length");
+            const Frame *kf = kfs[(size_t)F.kf_id], *cand = kfs[(size_t)F.cand_kf_id];
+            if (!F.pairs.empty() && (kf->left.empty() || cand->left.empty()))
+                return refuse("LocalFusion: the keyframe's feature list was released when it left the window (SetKeepKeyframeFeatures)");
+            std::vector<std::pair<int, int>> &o = order[(size_t)j];
+            o = F.pairs;
+            std::sort(o.begin(), o.end());                                // std::set<pair<cand feature, cur feature>>: ascending lexicographic
+            for (size_t i = 0; i < o.size(); ++i) {
+                if (o[i].first < 0 || (size_t)o[i].first >= cand->left.size() || o[i].second < 0 || (size_t)o[i].second >= kf->left.size())
+                    return refuse("LocalFusion: a pair's index is not a feature of its keyframe");
+                if (i > 0 && o[i] == o[i - 1]) return refuse("LocalFusion: a pair is repeated");
+            }
+            if (resident() && st.last != kf)
+                return refuse("LocalFusion: with resident tracking the last frame's features are held only by the kernel provider once it is not the keyframe itself; call it after the keyframe's step");
+        }
+        Flush();
+        // gather
+        std::vector<svslam_lf_job> lj((size_t)n);
+        std::vector<double> poses, pts;
+        std::vector<int> obs_ptr(1, 0), obs_kf, pt_kf;
+        for (int j = 0; j < n; ++j) {
+            const FusionJob &F = jobs[(size_t)j];
+            Stream &st = *streams_[F.stream];
+            Map &m = st.map;
+            const Frame *kf = m.keyframes_[(size_t)F.kf_id];
+            svslam_lf_job &J = lj[(size_t)j];
+            std::memset(&J, 0, sizeof(J));
+            J.kf_ofs = (int)(poses.size() / 7); J.nkf = (int)m.active_keyframes_.size(); J.pt_ofs = (int)(pts.size() / 3); J.npt = (int)m.active_landmarks_.size();
+            J.cur = J.last = -1;
+            for (int i = 0; i < J.nkf; ++i) {
+                const Frame *a = m.active_keyframes_[(size_t)i];
+                poses.insert(poses.end(), a->pose.v, a->pose.v + 7);
+                if (a == kf) J.cur = i;
+                if (a == st.last) J.last = i;
+            }
+            std::memcpy(J.T_cur, kf->pose.v, 56); std::memcpy(J.T_corr, F.T_corr.v, 56); std::memcpy(J.T_last, st.last->pose.v, 56);
+            auto row_of = [&](const Frame *f) {
+                for (int i = 0; i < J.nkf; ++i) if (m.active_keyframes_[(size_t)i] == f) return i;
+                return (J.cur < 0 && f == kf) ? J.nkf : -1;
+            };
+            for (MapPoint *mp : m.active_landmarks_) {
+                pts.insert(pts.end(), mp->pos, mp->pos + 3);
+                for (const ObsRef &o : mp->observations)
+                    obs_kf.push_back(m.Known(feat_of(o).mp) ? row_of(o.frame) : -1);      // the feature still names A landmark of the map
+                obs_ptr.push_back((int)obs_kf.size());
+            }
+        }
+        pt_kf.assign(pts.size() / 3 + 1, -1);
+        poses.push_back(0); pts.push_back(0); obs_kf.push_back(0);           // data() of an empty vector may be null
+        if (k_.local_fusion(n, lj.data(), (int)(poses.size() / 7), poses.data(), (int)(pts.size() / 3), pts.data(), obs_ptr.data(),
+                            (int)obs_kf.size() - 1, obs_kf.data(), pt_kf.data()) != 0)
+            return refuse(std::string("LocalFusion: ") + k_.last_error());
+        // write back, then the replacement
+        if (stats) stats->clear();
+        std::vector<int> up;
+        for (int j = 0; j < n; ++j) {
+            const FusionJob &F = jobs[(size_t)j];
+            Stream &st = *streams_[F.stream];
+            Map &m = st.map;
+            Frame *kf = m.keyframes_[(size_t)F.kf_id], *cand = m.keyframes_[(size_t)F.cand_kf_id];
+            const svslam_lf_job &J = lj[(size_t)j];
+            FusionStats S;
+            S.nkf = J.nkf; S.npt = J.npt; S.n_unanchored = J.n_unanchored;
+            for (int i = 0; i < J.npt; ++i) std::memcpy(m.active_landmarks_[(size_t)i]->pos, &pts[3 * ((size_t)J.pt_ofs + (size_t)i)], 24);
+            for (int i = 0; i < J.nkf; ++i) m.active_keyframes_[(size_t)i]->pose = SE3(&poses[7 * ((size_t)J.kf_ofs + (size_t)i)]);
+            if (J.last < 0) st.last->pose = SE3(J.T_last);
+            for (const std::pair<int, int> &pr : order[(size_t)j]) {
+                ++S.pairs;
+                const long lid = cand->left[(size_t)pr.first].mp;
+                MapPoint *mp_loop = m.point(lid);
+                if (!mp_loop && (mp_loop = m.Revive(lid))) ++S.revived;
+                if (!mp_loop) continue;
+                Feature &fq = kf->left[(size_t)pr.second];
+                MapPoint *mp_curr = m.point(fq.mp);
+                if (mp_curr) {
+                    std::vector<ObsRef> obs;                              // GetObs() hands out a copy: mp_loop may be mp_curr
+                    for (const ObsRef &o : mp_curr->observations) obs.push_back(o);
+                    for (const ObsRef &o : obs) { m.AddObservation(mp_loop, o); feat_of(o).mp = mp_loop->id; ++S.repointed; }
+                    if (mp_curr == mp_loop) ++S.same_deleted; else ++S.merged;
+                    m.RemoveLandmark(mp_curr);
+                } else if (m.DropArchived(fq.mp)) ++S.merged;             // a dead landmark: no observation to move, nothing re-pointed, removed
+                else { fq.mp = mp_loop->id; ++S.repointed; }
+            }
+            if (stats) stats->push_back(S);
+            up.push_back(F.stream);
+        }
+        if (resident() && !up.empty()) UploadFeatures(up);
+        return true;
+    }
+
     // LoopClosure::AddNewKeyFrame (src/loopclosure.cpp:182-198) and one turn of LoopClosurePipeline (:801-872) for every stream whose
     // last step made a keyframe, synchronously, after DescribeNewKeyframes.  vecs holds one global descriptor of dim floats per
     // stream, [nstreams][dim]; the rows of streams without a new keyframe are not read.
@@ -931,17 +1119,22 @@ public:
     //   4. an ACCEPTED pair is a loop edge already (VerifyLoops records it); it sets the stream's last_closed and is NOT stored (:861, :868)
     //   5. every other keyframe is appended to the store, in one call (:870)
     // A keyframe whose vector cannot be normalised (BAD_VECTOR) is not stored either; the reference would store NaNs.  LocalFusion
-    // (:858) is not done: the result carries the LoopResult for it.  A keyframe is handled once: a second call after the same step
+    // (:858) is done only when LoopDetectParams::local_fusion asks for it; the result carries the LoopResult for it either way.  A keyframe is handled once: a second call after the same step
     // finds nothing to do.  False (last_error(), nothing done): device_map = 1, a store that was not configured, a new keyframe
     // that was never described, a stream whose store is full, the provider's refusal.
     // vecs == nullptr: the vectors are computed here by the configured network (ConfigureGlobalDescriptor), for the keyframes this
     // call handles; refused when no network is configured, or when the store's dim is not the network's.
-    struct LoopDetectParams { svslam_lc_params cand; svslam_loop_params verify; long keyframes_to_ignore_after_loop; };
+    // local_fusion (default off: the call is what it was): the call ends with ONE LocalFusion call for every stream whose pair was
+    // ACCEPTED with need_correction (LoopClosureUpdate, :594-597, :858); its pairs are the match rows whose candidate feature had a
+    // landmark (KeypointMatches_, :340-366), mapped through desc_feat_indx.  LoopDetection::fused / fusion report it.
+    struct LoopDetectParams { svslam_lc_params cand; svslam_loop_params verify; long keyframes_to_ignore_after_loop; bool local_fusion = false; };
     struct LoopDetection {
         bool is_keyframe = false, skipped = false, searched = false, verified = false, stored = false;
         long kf_id = -1;
         svslam_lc_job cand = {};          // status, cand_kf, best_sim, best_kf, n_weak, n_compared when searched
         LoopResult loop;                  // when verified
+        bool fused = false;               // LoopDetectParams::local_fusion: LocalFusion ran for this stream
+        FusionStats fusion;               // when fused
     };
     bool DetectLoops(const float *vecs, const LoopDetectParams &params, std::vector<LoopDetection> *results)
     {
@@ -1008,6 +1201,30 @@ public:
             return refuse(std::string("DetectLoops: ") + k_.last_error());
         for (int s : as) out[(size_t)s].stored = true;
         for (int s = 0; s < ns; ++s) if (fresh[(size_t)s]) fresh[(size_t)s]->loop_checked = true;
+        if (params.local_fusion) {
+            std::vector<FusionJob> fj;
+            ArchiveCache archive;
+            for (size_t i = 0; i < pairs.size(); ++i) {
+                const LoopDetection &D = out[(size_t)pairs[i].stream];
+                if (D.loop.status != SVSLAM_LOOP_ACCEPTED || !D.loop.need_correction) continue;
+                const std::vector<Frame *> &kfs = streams_[pairs[i].stream]->map.keyframes_;
+                const Frame *kf = kfs[(size_t)pairs[i].kf_id], *cand = kfs[(size_t)pairs[i].cand_kf_id];
+                FusionJob F;
+                F.stream = pairs[i].stream; F.kf_id = pairs[i].kf_id; F.cand_kf_id = pairs[i].cand_kf_id; F.T_corr = D.loop.T_corr;
+                for (size_t r = 0; r < D.loop.match_c.size(); ++r) {
+                    const int ci = cand->desc_feat_indx[(size_t)D.loop.match_c[r]], qi = kf->desc_feat_indx[(size_t)D.loop.match_q[r]];
+                    double p[3];
+                    if (LandmarkPosition(F.stream, cand->left[(size_t)ci].mp, archive, p)) F.pairs.emplace_back(ci, qi);      // has_xyz
+                }
+                fj.push_back(std::move(F));
+            }
+            std::vector<FusionStats> fs;
+            if (!fj.empty()) {
+                // the detection itself has taken effect by now (loop edges, the store): the caller gets its results with the refusal
+                if (!LocalFusion(fj, &fs)) { last_detections_ = out; if (results) *results = std::move(out); return false; }
+                for (size_t i = 0; i < fj.size(); ++i) { out[(size_t)fj[i].stream].fused = true; out[(size_t)fj[i].stream].fusion = fs[i]; }
+            }
+        }
         last_detections_ = out;
         if (results) *results = std::move(out);
         return true;

@@ -108,6 +108,19 @@ class LoopDetection(C.Structure):
                 ("n_weak", C.c_int), ("n_compared", C.c_int), ("best_sim", C.c_float), ("loop", LoopResult)]
 
 
+class FusionJob(C.Structure):
+    _fields_ = [("stream", C.c_int), ("npairs", C.c_int), ("kf_id", C.c_longlong), ("cand_kf_id", C.c_longlong), ("pair_ofs", C.c_longlong),
+                ("T_corr", C.c_double * 7)]
+
+
+class FusionStats(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("fused", "nkf", "npt", "n_unanchored", "pairs", "merged", "revived", "repointed", "same_deleted", "reserved")]
+
+
+def _fusion_dict(r):
+    return {k: getattr(r, k) for k, _ in FusionStats._fields_ if k not in ("fused", "reserved")}
+
+
 def _bind(L):
     L.svs_pipe_create.restype = C.c_void_p
     L.svs_pipe_create.argtypes = [C.POINTER(PipeConfig), C.c_int, C.c_int]
@@ -153,6 +166,13 @@ def _bind(L):
         L.svs_pipe_loopdb_ids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
         L.svs_pipe_last_closed_keyframe.restype = C.c_longlong
         L.svs_pipe_last_closed_keyframe.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "svs_pipe_local_fusion"):
+        L.svs_pipe_local_fusion.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.svs_pipe_detect_loops_fused.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.svs_pipe_all_landmarks.restype = C.c_longlong
+        L.svs_pipe_all_landmarks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
+        L.svs_pipe_last_frame.restype = C.c_longlong
+        L.svs_pipe_last_frame.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     return L
 
 
@@ -403,13 +423,58 @@ class Pipeline:
             raise RuntimeError("svs_pipe_describe_global_new_keyframes refused: " + self.L.svs_pipe_last_error().decode())
         return v, n
 
-    def detect_loops(self, vecs=None, keyframes_to_ignore_after_loop=5, weak=None, strong=None, max_num_weak=None, min_gap=None, **loop_params):
+    def local_fusion(self, jobs):
+        """LoopClosure::LocalFusion for every job in one kernel call (svs_pipe_local_fusion), for a loop verified elsewhere (e.g.
+        verify_loops_stored): the active window, the active landmarks and the last frame move with the keyframe's corrected pose,
+        then the loop keyframe's landmarks replace the current keyframe's.  jobs: dicts with stream, kf_id, cand_kf_id, T_corr[7]
+        and pairs [(feature index in the loop keyframe, feature index in the keyframe)].  Returns one dict of statistics per job:
+        nkf, npt, n_unanchored, pairs, merged, revived, repointed, same_deleted.  A refusal changes nothing for any job."""
+        n = len(jobs)
+        arr = (FusionJob * max(n, 1))()
+        pairs = []
+        for i, j in enumerate(jobs):
+            pr = np.asarray(j.get("pairs", ()), np.int64).reshape(-1, 2)
+            arr[i] = FusionJob(int(j["stream"]), len(pr), int(j["kf_id"]), int(j["cand_kf_id"]), len(pairs),
+                               (C.c_double * 7)(*np.ascontiguousarray(j["T_corr"], np.float64).reshape(7)))
+            pairs.extend((int(a), int(b)) for a, b in pr)
+        P = np.ascontiguousarray(np.array(pairs, np.int32).reshape(-1, 2)) if pairs else np.zeros((1, 2), np.int32)
+        st = (FusionStats * max(n, 1))()
+        if self.L.svs_pipe_local_fusion(self.h, n, arr, P.ctypes.data_as(C.c_void_p), st) != 0:
+            raise RuntimeError("svs_pipe_local_fusion refused: " + self.L.svs_pipe_last_error().decode())
+        return [_fusion_dict(st[i]) for i in range(n)]
+
+    def all_landmarks(self, stream=0):
+        """Map::landmarks_ of a stream, id-ascending (svs_pipe_all_landmarks): dict(id [n], xyz [n, 3], observed_times [n], active [n],
+        anchor_kf [n]); dead landmarks come from the archive (float positions)"""
+        n = self.L.svs_pipe_all_landmarks(self.h, int(stream), None, 0)
+        if n < 0:
+            raise RuntimeError("svs_pipe_all_landmarks refused: " + self.L.svs_pipe_last_error().decode())
+        out = np.zeros((max(n, 1), 7))
+        if self.L.svs_pipe_all_landmarks(self.h, int(stream), out.ctypes.data_as(C.c_void_p), n) != n:
+            raise RuntimeError("svs_pipe_all_landmarks changed size between two calls")
+        out = out[:n]
+        return dict(id=out[:, 0].astype(np.int64), xyz=out[:, 1:4].copy(), observed_times=out[:, 4].astype(np.int64), active=out[:, 5] != 0,
+                    anchor_kf=out[:, 6].astype(np.int64))
+
+    def last_frame(self, stream=0):
+        """(pose[7], keyframe id or -1) of the frontend's last frame of a stream (svs_pipe_last_frame)"""
+        pose = np.zeros(7)
+        k = self.L.svs_pipe_last_frame(self.h, int(stream), pose.ctypes.data_as(C.c_void_p))
+        if k < -1:
+            raise RuntimeError("svs_pipe_last_frame refused: " + self.L.svs_pipe_last_error().decode())
+        return pose, int(k)
+
+    def detect_loops(self, vecs=None, keyframes_to_ignore_after_loop=5, weak=None, strong=None, max_num_weak=None, min_gap=None, local_fusion=False,
+                     **loop_params):
         """LoopClosure::AddNewKeyFrame + one turn of LoopClosurePipeline for every stream whose last step made a keyframe
         (svs_pipe_detect_loops), after describe_new_keyframes: skip rule, candidate search, verification, loop edge, store update.
         vecs: [nstreams, dim] global descriptors (rows of streams without a new keyframe are not read), or None: the network set by
         configure_global_descriptor computes them.  weak, strong, max_num_weak,
         min_gap: LC_DEFAULTS; loop_params: as verify_loops.  Returns one dict per stream: is_keyframe, skipped, searched, verified,
-        stored, kf_id, cand (status, cand_kf, best_sim, best_kf, n_weak, n_compared) or None, loop (as verify_loops) or None."""
+        stored, kf_id, cand (status, cand_kf, best_sim, best_kf, n_weak, n_compared) or None, loop (as verify_loops) or None.
+        local_fusion=True (svs_pipe_detect_loops_fused): every stream whose pair was ACCEPTED with need_correction is fused
+        (LoopClosure::LocalFusion) in one more kernel call; the dicts gain fused and fusion (the statistics of local_fusion, or None).
+        Off (the default) this is the call it was."""
         import importlib
         _svs = importlib.import_module(__package__)
         unknown = set(loop_params) - set(_svs.LOOP_DEFAULTS)
@@ -425,7 +490,11 @@ class Pipeline:
                             float(p["max_pose_distance"]), float(p["min_pose_difference"]), float(p["max_pose_difference"]),
                             int(p["seed"]) & 0xFFFFFFFF, 0)
         res = (LoopDetection * ns)()
-        if self.L.svs_pipe_detect_loops(self.h, v.ctypes.data_as(C.c_void_p) if v is not None else None, C.byref(D), C.byref(P), res) != 0:
+        fs = (FusionStats * ns)()
+        if local_fusion:
+            if self.L.svs_pipe_detect_loops_fused(self.h, v.ctypes.data_as(C.c_void_p) if v is not None else None, C.byref(D), C.byref(P), 1, res, fs) != 0:
+                raise RuntimeError("svs_pipe_detect_loops_fused refused: " + self.L.svs_pipe_last_error().decode())
+        elif self.L.svs_pipe_detect_loops(self.h, v.ctypes.data_as(C.c_void_p) if v is not None else None, C.byref(D), C.byref(P), res) != 0:
             raise RuntimeError("svs_pipe_detect_loops refused: " + self.L.svs_pipe_last_error().decode())
         out = []
         for s in range(ns):
@@ -443,6 +512,9 @@ class Pipeline:
                 d["loop"] = dict(status=l.status, n_matches=l.n_matches, n_points=l.n_points, n_inliers=l.n_inliers,
                                  need_correction=bool(l.need_correction), T_corr=np.array(l.T_corr), T_rel=np.array(l.T_rel), d=l.d,
                                  matches=m4[:l.n_matches].astype(np.int64))
+            if local_fusion:
+                d["fused"] = bool(fs[s].fused)
+                d["fusion"] = _fusion_dict(fs[s]) if fs[s].fused else None
             out.append(d)
         return out
 
