@@ -509,6 +509,56 @@ int svslam_brief_describe_batch(svslam_ctx *ctx, int njobs, svslam_brief_job *jo
                                 int total_pts, const float *xy, uint8_t *desc /* [total_pts][32] */, int *desc_pt /* [total_pts] */);
 int svslam_brief_default_pattern(int8_t out[1024]);
 
+/* ---- ORB keypoint detector: oriented multi-scale FAST corners of a pyramid slot ----------
+ * Replaces cv::ORB::create(num_features)->detect(img, kps, mask) of Frontend::DetectFeatures with keypoint_feature_detector: ORB
+ * (src/frontend.cpp:20-33, :51).  ORB's defaults: scale factor 1.2f, 8 levels, edge threshold 31, first level 0, HARRIS_SCORE, patch
+ * size 31, FAST threshold 20.  One job is level 0 of one pyramid slot (w x h, u8) and a range of rect centres (the existing features,
+ * the rect_xy input and rule of svslam_gftt_batch).  OpenCV is on neither machine, so parity with it is unpinned; the contract is this
+ * text and tests/ref_orb.py, met bit for bit, every step integer, written-out f32, or f64 on the host:
+ *   levels   scale_L = (float)pow((double)1.2f, L); inv_L = 1.f / scale_L; w_L = rint((float)w inv_L), h_L alike, half to even
+ *   quotas   factor = (float)(1.0 / (double)1.2f); nd = nfeatures (1 - factor) / (1 - (float)pow(factor, nlevels)) in f32, left to
+ *            right; n_L = rint(nd), nd *= factor for L < nlevels - 1; n_last = max(nfeatures - sum, 0)
+ *   pyramid  level L from level L - 1 by the bit-exact bilinear resize.  Per axis s = 1.0 / ((double)dst / (double)src),
+ *            f = s (d + 0.5) - 0.5 in double, i = floor(f); i < 0: sample 0 with weight 256; i >= src - 1: sample src - 1 with weight
+ *            256; else c1 = rint((f - i) 256), c0 = 256 - c1 on samples i, i + 1.  Horizontal t = p[i] c0 + p[i + 1] c1 kept in full,
+ *            vertical v = t0 c0 + t1 c1, out = (v + 32768) >> 16
+ *   mask     level 0: 255, and 0 inside the inclusive square [rint(pt - 10), rint(pt + 10)] of every rect centre, clipped to the
+ *            image; level L >= 1: the same resize of the level L - 1 mask, then <= 254 becomes 0
+ *   FAST     9 of 16 on the radius-3 circle at 3 <= x < w_L - 3, 3 <= y < h_L - 3, strict compares against v +- fast_threshold;
+ *            score = the largest threshold at which the pixel is still a corner (max over the 16 arcs and both polarities of the
+ *            arc's minimum signed difference, minus 1), 0 for a non-corner; a corner survives iff its score is strictly greater than
+ *            its 8 neighbours' scores
+ *   filters  border: edge <= x < w_L - edge, edge <= y < h_L - edge; then mask: mask_L[y][x] != 0
+ *   cut 1    m = 2 n_L; with more than m survivors all with score >= the m-th largest are kept, ties included; m == 0: none
+ *   Harris   7 x 7 block; per block pixel in int32 Ix = (p[+1] - p[-1]) 2 + (p[-row+1] - p[-row-1]) + (p[+row+1] - p[+row-1]),
+ *            Iy = (p[+row] - p[-row]) 2 + (p[+row-1] - p[-row-1]) + (p[+row+1] - p[-row+1]); a += Ix Ix, b += Iy Iy, c += Ix Iy;
+ *            scale = 1.f / (4 * 7 * 255.f), s4 = scale scale scale scale; response = ((float)a (float)b - (float)c (float)c -
+ *            0.04f ((float)a + (float)b) ((float)a + (float)b)) s4 in f32, left to right, no contraction
+ *   cut 2    with more than n_L points left all with response >= the n_L-th largest are kept (float compare, ties included)
+ *   angle    intensity centroid over the circular patch of half-size 15 (umax: csrc/k_orb.h), m10 = sum u I, m01 = sum v I in int32;
+ *            angle = fastAtan2((float)m01, (float)m10) in degrees, [0, 360): ax = |x|, ay = |y|; ax >= ay: c = ay / (ax +
+ *            (float)DBL_EPSILON), a = (((p7 c c + p5) c c + p3) c c + p1) c; else c = ax / (ay + (float)DBL_EPSILON), a = 90 - the
+ *            same; x < 0: a = 180 - a; y < 0: a = 360 - a; p1, p3, p5, p7 = 0.9997878412794807f, -0.3258083974640975f,
+ *            0.1555786518463281f, -0.04432655554792128f, each times (float)(180 / pi); IEEE f32 division, no FMA
+ *   output   x = (float)xi scale_L, y = (float)yi scale_L, size = 31 scale_L, angle, response, octave = L
+ * Order (a declared deviation: OpenCV's comes out of nth_element and is unspecified): level ascending, row-major in level coordinates
+ * inside a level.  Duplicates across levels are kept, as there.  n_found is the count these rules give, n_out = min(n_found, max_out);
+ * the first n_out rows in that order are written to out[job][0 .. n_out), the rows behind them are left as they were.
+ * Errors, nothing written: nfeatures < 1 (after the default) or above 2^24; nlevels outside 1..8; fast_threshold outside 1..254;
+ * edge < 16 (the orientation reads radius 15, Harris radius 4); max_out < 1; a slot out of range; a rect range that leaves the array;
+ * no memory for the call's buffer (allocated inside the call on demand and kept; a large call is split into chunks under a byte
+ * budget; svslam_limits has no say in it, njobs is not bounded by max_jobs).  Valid no-ops: njobs == 0, an image none of whose levels
+ * has an interior (w_L <= 2 edge or h_L <= 2 edge).  A rect centre that is not a number masks nothing.  A job's result does not depend
+ * on the other jobs of the call, and two calls on the same inputs give the same bits.
+ * svslam_orb_read_level is a test hook: image and mask (tight, w_L x h_L; either pointer may be NULL) of a level of a job of the last
+ * call, as long as the job was in the last chunk of that call. */
+typedef struct svslam_orb_job { int slot; int rect_ofs, nrect; int n_out, n_found /* out */; int reserved; } svslam_orb_job;
+typedef struct svslam_orb_params { int nfeatures; int nlevels; int fast_threshold; int edge; } svslam_orb_params;   /* 0 in a field: ORB's default (500, 8, 20, 31) */
+typedef struct svslam_orb_kp { float x, y, size, angle, response; int octave; } svslam_orb_kp;
+int svslam_orb_detect_batch(svslam_ctx *ctx, int njobs, svslam_orb_job *jobs, const svslam_orb_params *params,
+                            int total_rects, const float *rect_xy, int max_out, svslam_orb_kp *out /* [njobs][max_out] */);
+int svslam_orb_read_level(svslam_ctx *ctx, int job, int level, uint8_t *img, uint8_t *mask, int *w, int *h);
+
 /* ---- loop candidate search: a resident store of global image descriptors and the two-threshold rule ----------
  * Replaces stage 1 of the reference's loop closure, LoopClosure::LoopKeyframeCandidate (src/loopclosure.cpp:227-284) with
  * SimilarityScore (:173-180) and the normalisation of :128.  The global descriptor itself (the reference's MobileNetV2 vector of 1280
@@ -866,7 +916,8 @@ int svslam_sync(svslam_ctx *ctx);
  * 16 loop_candidates (units = rows compared, summed over the jobs; appended after 15, nothing moved),
  * 17 global_desc (units = jobs; appended after 16, nothing moved),
  * 18 colour (the conversion kernel of svslam_pyramid_bgr_batch; units = images; appended after 17, nothing moved),
- * 19 local_fusion (units = jobs; appended after 18, nothing moved).
+ * 19 local_fusion (units = jobs; appended after 18, nothing moved),
+ * 20 orb (svslam_orb_detect_batch; units = jobs; appended after 19, nothing moved).
  * Development families follow and are NOT stable numbers: with stereo_bm taking 6, the
  * per-kernel split moved from 6-9 to 7-10 and the local-BA solver interval from 10 to 11.
  * A caller that passed those raw numbers must move with them (Python addresses them by name). */

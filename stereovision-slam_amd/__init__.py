@@ -22,6 +22,7 @@ ABI_SYMBOLS = [
     "svslam_pyramid_read_padded", "svslam_stereo_bm_batch", "svslam_stereo_bm_strip_rows", "svslam_dense_cloud_batch", "svslam_cloud_sor_batch", "svslam_cloud_voxel_grid", "svslam_debug_cloud_sor_climbs",
     "svslam_colour_reserve", "svslam_pyramid_bgr_batch", "svslam_colour_read", "svslam_dense_cloud_bgr_batch", "svslam_lk_batch", "svslam_gftt_batch", "svslam_gftt_eigmap", "svslam_triangulate_batch",
     "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect", "svslam_pose_graph_batch", "svslam_local_fusion_batch", "svslam_loop_verify_batch", "svslam_brief_describe_batch", "svslam_brief_default_pattern",
+    "svslam_orb_detect_batch", "svslam_orb_read_level",
     "svslam_loopdb_configure", "svslam_loopdb_append_batch", "svslam_loop_candidates_batch", "svslam_loopdb_count", "svslam_loopdb_read",
     "svslam_gdesc_configure", "svslam_gdesc_dim", "svslam_gdesc_describe_batch", "svslam_gdesc_mobilenet_v2",
     "svslam_track_batch", "svslam_rtrack_batch", "svslam_rtrack_upload",
@@ -46,6 +47,8 @@ CLOUD_FAMILIES = {"cloud_filter": 12}      # the outlier removal and the voxel g
 LOOP_FAMILIES = {"pose_graph": 13, "loop_verify": 14, "brief": 15, "loop_candidates": 16, "global_desc": 17, "local_fusion": 19}
 # svslam_pyramid_bgr_batch's conversion kernel (units = images), appended after 17; a dictionary of its own: the dense program's, not the per-frame loop's
 COLOUR_FAMILIES = {"colour": 18}
+# svslam_orb_detect_batch (units = jobs), appended after 19; a dictionary of its own: bench.py's sums over FAMILIES see nothing new
+ORB_FAMILIES = {"orb": 20}
 # the HIP kernel(s) behind each timing family at the batch operating point (what a rocprofv3 --kernel-trace --stats row is named)
 FAMILY_KERNELS = {"pyramid": ["k_pyr_fused"], "lk": ["k_lk"], "gftt": ["k_gftt_eig3", "k_gftt_select2"], "triangulate": ["k_triangulate"],
                   "pose_only": ["k_pose_only"], "local_ba": ["k_dmap_ba_gather", "k_ba_build", "k_local_ba_t", "k_dmap_ba_scatter"],
@@ -54,6 +57,7 @@ FAMILY_KERNELS = {"pyramid": ["k_pyr_fused"], "lk": ["k_lk"], "gftt": ["k_gftt_e
                   "pose_graph": ["k_pose_graph"], "local_fusion": ["k_local_fusion"], "loop_verify": ["k_loop_verify"], "brief": ["k_brief_filter", "k_brief_describe"],
                   "loop_candidates": ["k_lc_candidates"],
                   "colour": ["k_bgr_prepare"],
+                  "orb": ["k_orb_fill", "k_orb_rects", "k_orb_resize", "k_orb_fast", "k_orb_select", "k_orb_emit"],
                   "global_desc": ["k_gd_prep", "k_gd_conv3", "k_gd_dw3", "k_gd_pw_mfma", "k_gd_pool"]}
 
 
@@ -182,6 +186,18 @@ class BriefParams(C.Structure):
     _fields_ = [("pattern", C.c_void_p), ("angle_deg", C.c_float), ("edge", C.c_int)]
 
 
+class OrbJob(C.Structure):
+    _fields_ = [("slot", C.c_int), ("rect_ofs", C.c_int), ("nrect", C.c_int), ("n_out", C.c_int), ("n_found", C.c_int), ("reserved", C.c_int)]
+
+
+class OrbParams(C.Structure):
+    _fields_ = [("nfeatures", C.c_int), ("nlevels", C.c_int), ("fast_threshold", C.c_int), ("edge", C.c_int)]
+
+
+# svslam_orb_kp as a structured array's row
+ORB_KP = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"), ("octave", "i4")])
+
+
 class BmParams(C.Structure):
     _fields_ = [("num_disparities", C.c_int), ("block_size", C.c_int), ("pre_filter_cap", C.c_int),
                 ("texture_threshold", C.c_int), ("uniqueness_ratio", C.c_int), ("reserved", C.c_int)]
@@ -276,6 +292,8 @@ def load():
         L.svslam_gdesc_configure.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
         L.svslam_gdesc_describe_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.svslam_gdesc_dim.argtypes = [C.c_void_p]
+        L.svslam_orb_detect_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.svslam_orb_read_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.svslam_dev_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         L.svslam_dev_free.argtypes = [C.c_void_p, C.c_void_p]
         L.svslam_dev_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -421,7 +439,7 @@ class Context:
 
     def timing_get(self, family):
         ms, n, u = C.c_double(), C.c_longlong(), C.c_longlong()
-        fam = next(t[family] for t in (FAMILIES, KERNEL_FAMILIES, DENSE_FAMILIES, CLOUD_FAMILIES, LOOP_FAMILIES, COLOUR_FAMILIES, DEBUG_FAMILIES) if family in t)
+        fam = next(t[family] for t in (FAMILIES, KERNEL_FAMILIES, DENSE_FAMILIES, CLOUD_FAMILIES, LOOP_FAMILIES, COLOUR_FAMILIES, ORB_FAMILIES, DEBUG_FAMILIES) if family in t)
         self._chk(self.L.svslam_timing_get(self.h, fam, C.byref(ms), C.byref(n), C.byref(u)), "timing")
         return ms.value, n.value, u.value
 
@@ -886,6 +904,35 @@ class Context:
         desc = np.zeros((total, 32), np.uint8); dpt = np.zeros(total, np.int32)
         self._chk(self.L.svslam_brief_describe_batch(self.h, n, arr, C.byref(P), total, _p(XY), _p(desc), _p(dpt)), "brief_describe")
         return [(desc[j.pt_ofs:j.pt_ofs + j.n_desc].copy(), dpt[j.pt_ofs:j.pt_ofs + j.n_desc].copy(), j.n_desc) for j in arr]
+
+    # ---- ORB detector --------------------------------------------------------------
+    def orb_detect(self, jobs, max_out=2000, nfeatures=0, nlevels=0, fast_threshold=0, edge=0):
+        """ORB keypoints of level 0 of pyramid slots, all jobs in one call (svslam_orb_detect_batch).
+        jobs: list of (slot, rect_xy [n, 2] or None), the rects being the centres of the existing features (as for gftt).
+        A parameter of 0 is ORB's default (500, 8, 20, 31).
+        returns per job (keypoints, n_found): a structured array (ORB_KP) of the first min(n_found, max_out) keypoints, level
+        ascending and row-major inside a level, and the count the rules give."""
+        n = len(jobs)
+        arr = (OrbJob * max(n, 1))()
+        rects, ofs = [], 0
+        for i, (slot, r) in enumerate(jobs):
+            r = np.zeros((0, 2), np.float32) if r is None else _f32(r, 2)
+            arr[i].slot, arr[i].rect_ofs, arr[i].nrect = int(slot), ofs, r.shape[0]
+            ofs += r.shape[0]
+            rects.append(r)
+        rect = np.ascontiguousarray(np.concatenate(rects)) if ofs else np.zeros((1, 2), np.float32)
+        out = np.zeros((max(n, 1), max(int(max_out), 1)), ORB_KP)
+        P = OrbParams(int(nfeatures), int(nlevels), int(fast_threshold), int(edge))
+        self._chk(self.L.svslam_orb_detect_batch(self.h, n, arr, C.byref(P), ofs, _p(rect), int(max_out), _p(out)), "orb_detect")
+        return [(out[i, :arr[i].n_out].copy(), int(arr[i].n_found)) for i in range(n)]
+
+    def orb_read_level(self, job, level):
+        """test hook: (image, mask) of a pyramid level of a job of the last orb_detect call (svslam_orb_read_level)"""
+        w, h = C.c_int(0), C.c_int(0)
+        self._chk(self.L.svslam_orb_read_level(self.h, int(job), int(level), None, None, C.byref(w), C.byref(h)), "orb_read_level")
+        img = np.zeros((h.value, w.value), np.uint8); mask = np.zeros((h.value, w.value), np.uint8)
+        self._chk(self.L.svslam_orb_read_level(self.h, int(job), int(level), _p(img), _p(mask), C.byref(w), C.byref(h)), "orb_read_level")
+        return img, mask
 
     # ---- loop candidate search ---------------------------------------------------
     def loopdb_configure(self, nstreams, capacity, dim=1280):

@@ -55,6 +55,7 @@ typedef enum { ncclDouble = 8 } ncclDataType_t;
 #include "k_loop_candidates.h"
 #include "k_global_desc.h"
 #include "k_colour.h"
+#include "k_orb.h"
 
 #define SVSLAM_DMAP_CHUNK 512     /* keyframe jobs per svslam_dmap_keyframe_batch call the staging arena is sized for */
 #define SVSLAM_DMAP_EVICT_PER_JOB 512   /* evicted-landmark records per job of a call (shared by the call's jobs; the surplus waits) */
@@ -74,6 +75,7 @@ enum { FAM_PYR = 0, FAM_LK, FAM_GFTT, FAM_TRI, FAM_POSE, FAM_BA,
        FAM_GD,         // 17: "global_desc", svslam_gdesc_describe_batch (units = jobs); appended, nothing moved
        FAM_COL,        // 18: "colour", k_bgr_prepare of svslam_pyramid_bgr_batch (units = images); appended, nothing moved
        FAM_LF,         // 19: "local_fusion", svslam_local_fusion_batch (units = jobs); appended, nothing moved
+       FAM_ORB,        // 20: "orb", svslam_orb_detect_batch (units = jobs); appended, nothing moved
        FAM_COUNT };
 
 struct Timing {
@@ -143,6 +145,9 @@ struct svslam_ctx {
     DevBuf br;
     // local fusion (svslam_local_fusion_batch): the same arrangement
     DevBuf lf;
+    // ORB detector (svslam_orb_detect_batch): one device buffer (tables, jobs, rects, results, the jobs' levels, maps and lists of a
+    // chunk) and its pageable host mirror of the uploaded part and the results; the last call's plan stays for svslam_orb_read_level
+    struct : DevBuf { OrbPlan plan; bool have = false; } orb;
     // loop candidates: the resident store of normalised global descriptors (S on the device, H its bookkeeping) and a call's staging
     struct : DevBuf { LcStore S = {}; LcHost H; } lc;
     // global descriptor (svslam_gdesc_*): the configured network, its parameters and resize tables on the device, the workspace of a
@@ -853,4 +858,5 @@ int svslam_timing_get(svslam_ctx *c, int family, double *total_ms, long long *la
 #include "api_sba.h"
 #include "api_dmap.h"
 #include "api_loop.h"
+#include "api_orb.h"
 #include "api_debug.h"

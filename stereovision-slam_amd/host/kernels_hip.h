@@ -108,6 +108,9 @@ public:
     int gftt(int n, const svslam_gftt_job *jobs, int total_rects, const float *rect_xy, int max_corners,
              double quality, double min_dist, float *out_xy, int *out_n)
     { return svslam_gftt_batch(ctx_, n, jobs, total_rects, rect_xy, max_corners, quality, min_dist, out_xy, out_n); }
+    int orb_detect(int n, svslam_orb_job *jobs, const svslam_orb_params *params, int total_rects, const float *rect_xy, int max_out,
+                   svslam_orb_kp *out)
+    { return svslam_orb_detect_batch(ctx_, n, jobs, params, total_rects, rect_xy, max_out, out); }
     int triangulate(int n, const svslam_tri_job *jobs, int total, const double *cam_l, const double *ext_l,
                     const double *cam_r, const double *ext_r, const float *uv_l, const float *uv_r,
                     double *xyz, uint8_t *ok)

@@ -52,6 +52,11 @@ typedef struct svs_pipe_counters {
 
 void *svs_pipe_create(const svs_pipe_config *cfg, int nstreams, int device);
 void svs_pipe_destroy(void *p);
+/* Which detector Frontend::DetectFeatures runs: 0 = GFTT (the default), 1 = ORB (keypoint_feature_detector: ORB of the reference's
+ * configuration, svslam_orb_detect_batch).  A setter and not a field of svs_pipe_config, whose layout the CPU twin shares.
+ * -1 (svs_pipe_last_error, nothing changed): another kind; a call after the first frame; ORB with device_map or resident_track (there
+ * GFTT is fused into the keyframe chain); a kernel provider without the ORB detector ("this kernel provider has no ORB detector"). */
+int svs_pipe_set_detector(void *p, int kind);
 const char *svs_pipe_last_error(void);
 /* Process-wide glibc malloc settings for a host that drives thousands of streams: the per-frame
  * Frame / feature-list churn otherwise makes every thread's heap top shrink and regrow (munmap /

@@ -91,6 +91,14 @@ void *svs_pipe_create(const svs_pipe_config *cfg, int nstreams, int device)
 
 void svs_pipe_destroy(void *p) { delete static_cast<PipeHandle *>(p); }
 
+int svs_pipe_set_detector(void *p, int kind)
+{
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    if (h->pipe->SetDetector(kind)) return 0;
+    g_err = h->pipe->last_error();
+    return -1;
+}
+
 static void copy_results(const PipeHandle *h, svs_frame_result *out)
 {
     for (size_t s = 0; s < h->res.size(); ++s) {

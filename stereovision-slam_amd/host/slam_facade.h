@@ -296,6 +296,10 @@ struct FrontendOptions {            // the hyper-parameters Frontend::Frontend()
     // parameters) that configures the network behind the global image descriptor at start (Pipeline::ConfigureGlobalDescriptor);
     // DetectLoop(out) then needs no vector from the caller and loop_descriptor_dim becomes the network's.  Empty (default): no network.
     std::string loop_global_descriptor;
+    // `keypoint_feature_detector: ORB` of the reference's configuration (src/frontend.cpp:20-33): 1 = the ORB detector
+    // (Pipeline::SetDetector, svslam_orb_detect_batch), which selects the host map; 0 (default, `GFTT`): goodFeaturesToTrack.
+    // Any other value of the key throws.  ORB with loop_descriptors = 1 throws: the descriptors are not steered per keypoint yet.
+    int detector = 0;
     static FrontendOptions FromConfig(const ConfigFile &c)
     {
         FrontendOptions o;
@@ -314,7 +318,11 @@ struct FrontendOptions {            // the hyper-parameters Frontend::Frontend()
         o.max_triangulation_depth = c.Num("max_triangulation_depth", o.max_triangulation_depth);
         o.num_active_keyframes = (int)c.Num("num_active_keyframes", o.num_active_keyframes);
         o.chi2_th = c.Num("chi2_th", o.chi2_th);
-        if (c.Str("keypoint_feature_detector", "GFTT") != "GFTT") throw SLAMException("Only the GFTT keypoint detector is on the GPU path");
+        const std::string det = c.Str("keypoint_feature_detector", "GFTT");
+        if (det == "ORB") o.detector = 1;
+        else if (det != "GFTT") throw SLAMException("Only the GFTT and ORB keypoint detectors are on the GPU path");
+        if (o.detector == 1 && o.loop_descriptors)
+            throw SLAMException("keypoint_feature_detector: ORB with loop_descriptors: 1 is not supported yet: the descriptors would ignore the keypoints' angle and octave");
         return o;
     }
 };
@@ -503,7 +511,9 @@ private:
         cfg.num_active_keyframes = opt_.num_active_keyframes; cfg.chi2_th = opt_.chi2_th;
         cfg.backend_on = 1;                        // gated by SetBackendEnabled: see SetBackend
         cfg.width = dw; cfg.height = dh; cfg.src_width = w; cfg.src_height = h;
-        const bool dmap = opt_.device_map != 0 && provider_has_device_map<K>(0) && cfg.num_active_keyframes + 1 <= 12;
+        if (opt_.detector == 1 && opt_.loop_descriptors)
+            throw SLAMException("keypoint_feature_detector: ORB with loop_descriptors: 1 is not supported yet: the descriptors would ignore the keypoints' angle and octave");
+        const bool dmap = opt_.device_map != 0 && provider_has_device_map<K>(0) && cfg.num_active_keyframes + 1 <= 12 && opt_.detector == 0;
         cfg.resident_track = dmap ? 1 : 0;         // host map: the host keeps the feature lists; device map: nothing per feature on the host
         cfg.device_map = dmap ? 1 : 0;
         cfg.cam_l = *camera_left_; cfg.cam_r = *camera_right_;
@@ -519,6 +529,11 @@ private:
         if (kernels_->set_low_latency(opt_.low_latency ? 1 : 0) != 0) throw SLAMException(std::string("low-latency shapes: ") + kernels_->last_error());
         if (kernels_->set_pose_only_xtol(opt_.pose_xtol) != 0) throw SLAMException(std::string("pose_xtol: ") + kernels_->last_error());
         pipe_.reset(new Pipeline<K>(cfg, *kernels_, 1, 1));
+        if (opt_.detector != 0 && !pipe_->SetDetector(opt_.detector)) {
+            const std::string why = pipe_->last_error();        // no pipeline is left behind that would detect with GFTT instead
+            pipe_.reset(); kernels_.reset();
+            throw SLAMException(why);
+        }
         if (opt_.loop_descriptors) pipe_->SetKeepKeyframeFeatures(true);
         if (!opt_.loop_global_descriptor.empty()) configure_global_descriptor();
         wire_backend(); wire_map();

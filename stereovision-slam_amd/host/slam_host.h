@@ -507,6 +507,10 @@ struct Stream {
 // ------------------------------------------------------------------ the staged pipeline
 // Every stage has the shape  [serial: sizes -> offsets]  [parallel over streams: fill the
 // batched arrays]  [ONE C-ABI call for all streams]  [parallel over streams: consume].
+// does the kernel provider offer the ORB detector (HipKernels::orb_detect)?  The providers of the CPU twins do not.
+template <class K> constexpr auto provider_has_orb(int) -> decltype(&K::orb_detect, true) { return true; }
+template <class K> constexpr bool provider_has_orb(long) { return false; }
+
 template <class K>
 class Pipeline {
 public:
@@ -535,6 +539,22 @@ public:
     const Counters &counters() const { return cnt_; }
     Stream &stream(int s) { return *streams_[s]; }
     bool map_on_host() const { return !(cfg_.device_map && cfg_.resident_track); }   // (svs_pipe_map_snapshot)
+    // Which detector DetectFeatures runs: 0 = GFTT (src/frontend.cpp:24, the default), 1 = ORB (:20-33).  A setter and not a field
+    // of the configuration, whose layout the CPU twin shares.  False (last_error(), nothing changed): another kind, a call after the
+    // first frame, a provider without orb_detect, or ORB with device_map / resident_track: there GFTT is fused into the keyframe chain.
+    bool SetDetector(int kind)
+    {
+        if (kind != 0 && kind != 1) return refuse("SetDetector: the detector is 0 (GFTT) or 1 (ORB)");
+        if (cnt_.frames > 0) return refuse("SetDetector: the detector is chosen before the first frame");
+        if (kind == 1) {
+            if (!provider_has_orb<K>(0)) return refuse("SetDetector: this kernel provider has no ORB detector");
+            if (cfg_.device_map || cfg_.resident_track)
+                return refuse("SetDetector: the ORB detector runs on the host-map path only (device_map and resident_track off)");
+        }
+        detector_ = kind;
+        return true;
+    }
+    int detector() const { return detector_; }
 
     // Frontend::AddFrame for every stream (src/frontend.cpp:690-721), in lockstep.
     // left/right: one image pointer per stream (host or device memory).
@@ -1661,6 +1681,48 @@ private:
         cnt_.pyr_left += (long long)IS.size(); cnt_.pyr_right += (long long)DS.size();
     }
 
+    // keypoint_feature_detector: ORB (src/frontend.cpp:20-33, :51): cv::ORB::create(num_features)->detect(img, kps, mask) through the
+    // provider's orb_detect with the rects DetectFeatures has filled; (x, y) of the keypoints are appended under the same max_pts /
+    // c_dropped rule as the corners.  Feature keeps x and y only for now: angle, octave, size and response are not stored.
+    // Keypoints the rules give beyond the call's 2 num_features rows (score and response ties) count as dropped.
+    void DetectOrb(const std::vector<int> &DS, int n, int ofs)
+    {
+        if constexpr (provider_has_orb<K>(0)) {
+            const int max_out = 2 * cfg_.num_features;
+            jobs_orb_.resize((size_t)n);
+            for (int i = 0; i < n; ++i) {
+                std::memset(&jobs_orb_[(size_t)i], 0, sizeof(svslam_orb_job));
+                jobs_orb_[(size_t)i].slot = jobs_gftt_[i].slot; jobs_orb_[(size_t)i].rect_ofs = jobs_gftt_[i].rect_ofs; jobs_orb_[(size_t)i].nrect = jobs_gftt_[i].nrect;
+            }
+            kps_orb_.resize((size_t)n * max_out);
+            svslam_orb_params P;
+            P.nfeatures = cfg_.num_features; P.nlevels = 0; P.fast_threshold = 0; P.edge = 0;          // ORB's defaults
+            { KTimer kt_(cnt_); check(k_.orb_detect(n, jobs_orb_.data(), &P, ofs, rects_.data(), max_out, kps_orb_.data()), "orb_detect"); }
+            long long t_h3 = now_ns();
+            pool_.parallel_for(n, [&](int i) {
+                Stream &st = *streams_[DS[i]];
+                int take = jobs_orb_[(size_t)i].n_out;
+                st.c_dropped += jobs_orb_[(size_t)i].n_found - take;
+                if (cfg_.max_pts > 0) {                                  // capacity of the kernel provider
+                    const int room = std::max(0, cfg_.max_pts - (int)st.current->left.size());
+                    if (take > room) { st.c_dropped += take - room; take = room; }
+                }
+                for (int c = 0; c < take; ++c) {
+                    Feature f;
+                    f.x = kps_orb_[(size_t)i * max_out + c].x;
+                    f.y = kps_orb_[(size_t)i * max_out + c].y;
+                    st.current->left.push_back(f);
+                }
+                st.c_corners += take;
+            });
+            cnt_.gftt_calls += n; cnt_.gftt_rects += ofs;
+            st_[3] += now_ns() - t_h3;
+        } else {
+            (void)DS; (void)n; (void)ofs;
+            throw std::runtime_error("this kernel provider has no ORB detector");
+        }
+    }
+
     // Frontend::DetectFeatures :36-70
     void DetectFeatures(const std::vector<int> &DS)
     {
@@ -1681,6 +1743,7 @@ private:
             size_t g = (size_t)jobs_gftt_[i].rect_ofs;
             for (const Feature &f : st.current->left) { rects_[2 * g] = f.x; rects_[2 * g + 1] = f.y; ++g; }
         });
+        if (detector_ == 1) { st_[3] += now_ns() - t_h3; DetectOrb(DS, n, ofs); return; }
         corners_.assign((size_t)n * cfg_.num_features * 2, 0.f);
         ncorners_.assign((size_t)n, 0);
         st_[3] += now_ns() - t_h3;
@@ -2110,6 +2173,9 @@ private:
     std::vector<double> up_xyz_;
     std::vector<svslam_lk_job> jobs_lk_;
     std::vector<svslam_gftt_job> jobs_gftt_;
+    int detector_ = 0;                              // SetDetector: 0 GFTT, 1 ORB
+    std::vector<svslam_orb_job> jobs_orb_;
+    std::vector<svslam_orb_kp> kps_orb_;
     std::vector<svslam_tri_job> jobs_tri_;
     std::vector<svslam_ba_job> jobs_ba_;
     std::vector<svslam_dmap_job> jobs_dm_;

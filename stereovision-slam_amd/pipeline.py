@@ -140,6 +140,8 @@ def _bind(L):
     L.svs_pipe_backend_ctx.argtypes = [C.c_void_p]
     L.svs_pipe_kernel_ctx.restype = C.c_void_p
     L.svs_pipe_kernel_ctx.argtypes = [C.c_void_p]
+    if hasattr(L, "svs_pipe_set_detector"):
+        L.svs_pipe_set_detector.argtypes = [C.c_void_p, C.c_int]
     if hasattr(L, "svs_pipe_add_loop_edge"):        # product library only (the CPU twins have no pose-graph provider)
         L.svs_pipe_add_loop_edge.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p]
         L.svs_pipe_pose_graph_optimization.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -191,14 +193,30 @@ def product_lib():
     return _product
 
 
+DETECTORS = {"GFTT": 0, "ORB": 1}
+
+
 class Pipeline:
-    def __init__(self, cfg=None, nstreams=1, device=0, lib=None):
+    def __init__(self, cfg=None, nstreams=1, device=0, lib=None, detector=None):
+        """detector: None (GFTT, the setter is not called), "GFTT" or "ORB" (svs_pipe_set_detector; ORB: host map only)"""
         self.L = _bind(lib) if lib is not None else product_lib()
         self.cfg = cfg or default_config()
         self.n = nstreams
         self.h = self.L.svs_pipe_create(C.byref(self.cfg), nstreams, device)
         if not self.h:
             raise RuntimeError("svs_pipe_create failed: " + self.L.svs_pipe_last_error().decode())
+        if detector is not None:
+            try:
+                self.set_detector(detector)
+            except Exception:
+                self.close()
+                raise
+
+    def set_detector(self, detector):
+        """which detector DetectFeatures runs, before the first frame: "GFTT" / 0 or "ORB" / 1"""
+        kind = DETECTORS[detector.upper()] if isinstance(detector, str) else int(detector)
+        if self.L.svs_pipe_set_detector(self.h, kind) != 0:
+            raise RuntimeError("svs_pipe_set_detector refused: " + self.L.svs_pipe_last_error().decode())
 
     def close(self):
         if self.h:
