@@ -559,6 +559,47 @@ int svslam_orb_detect_batch(svslam_ctx *ctx, int njobs, svslam_orb_job *jobs, co
                             int total_rects, const float *rect_xy, int max_out, svslam_orb_kp *out /* [njobs][max_out] */);
 int svslam_orb_read_level(svslam_ctx *ctx, int job, int level, uint8_t *img, uint8_t *mask, int *w, int *h);
 
+/* ---- ORB descriptors: rBRIEF at each keypoint's angle and octave ------------------------------------------------
+ * What cv::ORB::compute does with the keypoints cv::ORB::detect returned (LoopClosure::ExtractKeypointsDescriptor,
+ * src/loopclosure.cpp:131-171): a freshly detected feature is described on pyramid level `octave` with the test table turned by its own
+ * angle, a tracked one (cv::KeyPoint(pt, 7)) at -1 degree on level 0.  One job is level 0 of one pyramid slot and a range of
+ * svslam_orb_kp, the detector's output struct; size and response are ignored.  The contract, restated in tests/ref_orb_desc.py and met
+ * bit for bit; every step is integer, a written-out f32 step, or f64 on the host.  Parity with OpenCV is unpinned.
+ *   levels    scale_L, inv_L = 1.f / scale_L, w_L, h_L are those of svslam_orb_detect_batch; level L comes from level L - 1 by the same
+ *             bit-exact bilinear resize (the same functions of csrc/k_orb.h); no mask.  Only levels 1 .. Lmax are built, Lmax the largest
+ *             octave among the call's points: a call whose points are all octave 0 launches no resize and reserves no level storage
+ *   filter    in this order: a point is kept iff edge <= x < w - edge and edge <= y < h - edge (float compares on level-0 coordinates,
+ *             as in svslam_brief_describe_batch); then cx = rint(x inv_L), cy = rint(y inv_L), one f32 product each, rounded half to
+ *             even (inv_0 is exactly 1); on a level L >= 1 kept iff edge <= cx < w_L - edge and edge <= cy < h_L - edge (on level 0
+ *             the first test is the whole filter, as in svslam_brief_describe_batch: x = w - edge - 0.01 is kept and its centre is
+ *             w - edge, which edge >= reach + 4 keeps inside the image).  Kept points keep their order:
+ *             the kept rows of a job are the first n_desc rows of its range in desc and desc_pt, desc_pt[row] = the point's index
+ *             inside the job, rows behind n_desc are left as they were
+ *   rotation  per point, on the host: r = angle * (float)(pi / 180) in f32, a = (float)cos((double)r), b = (float)sin((double)r);
+ *             on the device, for each of the 512 table points: ix = rint(px a - py b), iy = rint(px b + py a), each product and each
+ *             sum rounded to f32 on its own (no contraction), the result rounded half to even.  cos and sin stay on the host because
+ *             the device's and the C library's differ in the last bit
+ *   reach     per call, from the table alone: the largest over the 512 table points of the smallest integer m with m^2 >= px^2 + py^2.
+ *             It bounds every rotated offset at every angle; 19 for the default table
+ *   blur, tests, packing   svslam_brief_describe_batch's: taps 18, 34, 49, 54, 49, 34, 18, (v + 32768) >> 16, strict <, byte t / 8,
+ *             bit t % 8, on the level-`octave` image around (cx, cy)
+ * params: pattern NULL = the default table of svslam_brief_default_pattern, edge 0 = 31, nlevels 0 = 8.
+ * Errors, nothing written: a job's range that leaves the arrays, ranges that do not ascend or overlap, a slot out of range, npts > 1024,
+ * a table entry whose two points coincide, edge < reach + 4, reach > 24, nlevels outside 1..8, an octave outside 0 .. nlevels - 1 or a
+ * non-finite angle (any finite float is accepted) at a point of a job, no memory for the call's buffer (allocated inside the call on demand and kept; a large call is
+ * split into chunks under a byte budget, njobs is not bounded by max_jobs).  Valid no-ops: njobs == 0, npts == 0.  A point whose level
+ * has no interior is dropped; non-finite coordinates fail the filter.  A job's result does not depend on the other jobs of the call,
+ * and two calls on the same inputs give the same bits.
+ * Declared deviations: (a) OpenCV sorts provided keypoints by level, the input order is kept here (the reference re-associates by
+ * position); (b) a centre that fails the level-L border test is dropped where OpenCV would read its 32-pixel reflected border: a
+ * detector keypoint never fails it (x = xi scale_L and rint(x inv_L) == xi there), a tracked one is octave 0.
+ * Property: with the default table and every point at angle -1, octave 0, the rows are those of
+ * svslam_brief_describe_batch(angle_deg = -1) bit for bit. */
+typedef struct svslam_orb_desc_job { int slot; int pt_ofs, npts; int n_desc /* out */; int reserved; } svslam_orb_desc_job;
+typedef struct svslam_orb_desc_params { const int8_t *pattern; int edge; int nlevels; int reserved; } svslam_orb_desc_params;   /* NULL / 0: default table, 31, 8 */
+int svslam_orb_describe_batch(svslam_ctx *ctx, int njobs, svslam_orb_desc_job *jobs, const svslam_orb_desc_params *params,
+                              int total_pts, const svslam_orb_kp *kps, uint8_t *desc /* [total_pts][32] */, int *desc_pt /* [total_pts] */);
+
 /* ---- loop candidate search: a resident store of global image descriptors and the two-threshold rule ----------
  * Replaces stage 1 of the reference's loop closure, LoopClosure::LoopKeyframeCandidate (src/loopclosure.cpp:227-284) with
  * SimilarityScore (:173-180) and the normalisation of :128.  The global descriptor itself (the reference's MobileNetV2 vector of 1280
@@ -917,7 +958,8 @@ int svslam_sync(svslam_ctx *ctx);
  * 17 global_desc (units = jobs; appended after 16, nothing moved),
  * 18 colour (the conversion kernel of svslam_pyramid_bgr_batch; units = images; appended after 17, nothing moved),
  * 19 local_fusion (units = jobs; appended after 18, nothing moved),
- * 20 orb (svslam_orb_detect_batch; units = jobs; appended after 19, nothing moved).
+ * 20 orb (svslam_orb_detect_batch; units = jobs; appended after 19, nothing moved),
+ * 21 orb_desc (svslam_orb_describe_batch; units = points; appended after 20, nothing moved).
  * Development families follow and are NOT stable numbers: with stereo_bm taking 6, the
  * per-kernel split moved from 6-9 to 7-10 and the local-BA solver interval from 10 to 11.
  * A caller that passed those raw numbers must move with them (Python addresses them by name). */

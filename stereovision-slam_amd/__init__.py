@@ -22,7 +22,7 @@ ABI_SYMBOLS = [
     "svslam_pyramid_read_padded", "svslam_stereo_bm_batch", "svslam_stereo_bm_strip_rows", "svslam_dense_cloud_batch", "svslam_cloud_sor_batch", "svslam_cloud_voxel_grid", "svslam_debug_cloud_sor_climbs",
     "svslam_colour_reserve", "svslam_pyramid_bgr_batch", "svslam_colour_read", "svslam_dense_cloud_bgr_batch", "svslam_lk_batch", "svslam_gftt_batch", "svslam_gftt_eigmap", "svslam_triangulate_batch",
     "svslam_pose_only_batch", "svslam_local_ba_batch", "svslam_local_ba_submit", "svslam_local_ba_collect", "svslam_pose_graph_batch", "svslam_local_fusion_batch", "svslam_loop_verify_batch", "svslam_brief_describe_batch", "svslam_brief_default_pattern",
-    "svslam_orb_detect_batch", "svslam_orb_read_level",
+    "svslam_orb_detect_batch", "svslam_orb_read_level", "svslam_orb_describe_batch",
     "svslam_loopdb_configure", "svslam_loopdb_append_batch", "svslam_loop_candidates_batch", "svslam_loopdb_count", "svslam_loopdb_read",
     "svslam_gdesc_configure", "svslam_gdesc_dim", "svslam_gdesc_describe_batch", "svslam_gdesc_mobilenet_v2",
     "svslam_track_batch", "svslam_rtrack_batch", "svslam_rtrack_upload",
@@ -49,6 +49,8 @@ LOOP_FAMILIES = {"pose_graph": 13, "loop_verify": 14, "brief": 15, "loop_candida
 COLOUR_FAMILIES = {"colour": 18}
 # svslam_orb_detect_batch (units = jobs), appended after 19; a dictionary of its own: bench.py's sums over FAMILIES see nothing new
 ORB_FAMILIES = {"orb": 20}
+# svslam_orb_describe_batch (units = points), appended after 20
+ORB_DESC_FAMILIES = {"orb_desc": 21}
 # the HIP kernel(s) behind each timing family at the batch operating point (what a rocprofv3 --kernel-trace --stats row is named)
 FAMILY_KERNELS = {"pyramid": ["k_pyr_fused"], "lk": ["k_lk"], "gftt": ["k_gftt_eig3", "k_gftt_select2"], "triangulate": ["k_triangulate"],
                   "pose_only": ["k_pose_only"], "local_ba": ["k_dmap_ba_gather", "k_ba_build", "k_local_ba_t", "k_dmap_ba_scatter"],
@@ -57,6 +59,7 @@ FAMILY_KERNELS = {"pyramid": ["k_pyr_fused"], "lk": ["k_lk"], "gftt": ["k_gftt_e
                   "pose_graph": ["k_pose_graph"], "local_fusion": ["k_local_fusion"], "loop_verify": ["k_loop_verify"], "brief": ["k_brief_filter", "k_brief_describe"],
                   "loop_candidates": ["k_lc_candidates"],
                   "colour": ["k_bgr_prepare"],
+                  "orb_desc": ["k_orbd_resize", "k_orbd_filter", "k_orbd_describe"],
                   "orb": ["k_orb_fill", "k_orb_rects", "k_orb_resize", "k_orb_fast", "k_orb_select", "k_orb_emit"],
                   "global_desc": ["k_gd_prep", "k_gd_conv3", "k_gd_dw3", "k_gd_pw_mfma", "k_gd_pool"]}
 
@@ -194,8 +197,26 @@ class OrbParams(C.Structure):
     _fields_ = [("nfeatures", C.c_int), ("nlevels", C.c_int), ("fast_threshold", C.c_int), ("edge", C.c_int)]
 
 
+class OrbDescJob(C.Structure):
+    _fields_ = [("slot", C.c_int), ("pt_ofs", C.c_int), ("npts", C.c_int), ("n_desc", C.c_int), ("reserved", C.c_int)]
+
+
+class OrbDescParams(C.Structure):
+    _fields_ = [("pattern", C.c_void_p), ("edge", C.c_int), ("nlevels", C.c_int), ("reserved", C.c_int)]
+
+
 # svslam_orb_kp as a structured array's row
 ORB_KP = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"), ("octave", "i4")])
+
+
+def orb_keypoints(kp):
+    """keypoints as an ORB_KP array: one already, or rows of (x, y, angle, octave)"""
+    if isinstance(kp, np.ndarray) and kp.dtype == ORB_KP:
+        return np.ascontiguousarray(kp).reshape(-1)
+    rows = np.asarray(kp, np.float64).reshape(-1, 4)
+    out = np.zeros(len(rows), ORB_KP)
+    out["x"], out["y"], out["angle"], out["octave"] = rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3].astype(np.int32)
+    return out
 
 
 class BmParams(C.Structure):
@@ -293,6 +314,7 @@ def load():
         L.svslam_gdesc_describe_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.svslam_gdesc_dim.argtypes = [C.c_void_p]
         L.svslam_orb_detect_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.svslam_orb_describe_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.svslam_orb_read_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.svslam_dev_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         L.svslam_dev_free.argtypes = [C.c_void_p, C.c_void_p]
@@ -439,7 +461,7 @@ class Context:
 
     def timing_get(self, family):
         ms, n, u = C.c_double(), C.c_longlong(), C.c_longlong()
-        fam = next(t[family] for t in (FAMILIES, KERNEL_FAMILIES, DENSE_FAMILIES, CLOUD_FAMILIES, LOOP_FAMILIES, COLOUR_FAMILIES, ORB_FAMILIES, DEBUG_FAMILIES) if family in t)
+        fam = next(t[family] for t in (FAMILIES, KERNEL_FAMILIES, DENSE_FAMILIES, CLOUD_FAMILIES, LOOP_FAMILIES, COLOUR_FAMILIES, ORB_FAMILIES, ORB_DESC_FAMILIES, DEBUG_FAMILIES) if family in t)
         self._chk(self.L.svslam_timing_get(self.h, fam, C.byref(ms), C.byref(n), C.byref(u)), "timing")
         return ms.value, n.value, u.value
 
@@ -933,6 +955,29 @@ class Context:
         img = np.zeros((h.value, w.value), np.uint8); mask = np.zeros((h.value, w.value), np.uint8)
         self._chk(self.L.svslam_orb_read_level(self.h, int(job), int(level), _p(img), _p(mask), C.byref(w), C.byref(h)), "orb_read_level")
         return img, mask
+
+    def orb_describe(self, jobs, pattern=None, edge=0, nlevels=0):
+        """ORB descriptors at keypoints of pyramid slots, each at its own angle and octave, all jobs in one call
+        (svslam_orb_describe_batch).  jobs: list of (slot, keypoints), keypoints a structured array (ORB_KP, what orb_detect
+        returns) or rows of (x, y, angle, octave).  pattern: [256, 4] int8 or None for the default table; edge, nlevels 0: 31, 8.
+        returns per job (desc [n_desc, 32] u8, desc_pt [n_desc] int32 = index of the row's point inside the job, n_desc)."""
+        n = len(jobs)
+        arr = (OrbDescJob * max(n, 1))()
+        parts, o = [], 0
+        for i, (slot, kp) in enumerate(jobs):
+            kp = orb_keypoints(kp)
+            arr[i].slot, arr[i].pt_ofs, arr[i].npts = int(slot), o, len(kp)
+            o += len(kp); parts.append(kp)
+        KP = np.ascontiguousarray(np.concatenate(parts)) if o else np.zeros(1, ORB_KP)
+        pat = None
+        if pattern is not None:
+            pat = np.ascontiguousarray(pattern, np.int8)
+            if pat.size != 1024:
+                raise ValueError("orb_describe: the table has %d entries, not 256 x 4" % pat.size)
+        P = OrbDescParams(pat.ctypes.data if pat is not None else None, int(edge), int(nlevels), 0)
+        desc = np.zeros((max(o, 1), 32), np.uint8); dpt = np.zeros(max(o, 1), np.int32)
+        self._chk(self.L.svslam_orb_describe_batch(self.h, n, arr, C.byref(P), o, _p(KP), _p(desc), _p(dpt)), "orb_describe")
+        return [(desc[j.pt_ofs:j.pt_ofs + j.n_desc].copy(), dpt[j.pt_ofs:j.pt_ofs + j.n_desc].copy(), j.n_desc) for j in arr[:n]]
 
     # ---- loop candidate search ---------------------------------------------------
     def loopdb_configure(self, nstreams, capacity, dim=1280):

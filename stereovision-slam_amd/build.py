@@ -7,7 +7,7 @@
   lib/lib<name>_host_emu.so a kernel header of csrc/ compiled for the host by tests/cpp/<name>_host_emu/emu.cpp, one per
                             entry of EMUS (lv, pg, lf, brief, lc, gd: k_loop_verify.h, k_pose_graph.h, k_local_fusion.h,
                             k_brief.h, k_loop_candidates.h, k_global_desc.h; bm, cf, colour, orb: k_stereo_bm.h,
-                            k_cloud_filter.h, k_colour.h, k_orb.h).  The build fails here, not in a test, when a kernel file stops being plain
+                            k_cloud_filter.h, k_colour.h, k_orb.h; orb_desc: k_orb_desc.h with the two it shares code with).  The build fails here, not in a test, when a kernel file stops being plain
                             C++ between the HIP qualifiers; the tests load the same libraries through build_emu
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the build container.
@@ -117,6 +117,7 @@ EMUS = {
     "cf": ([_C + "k_cloud_filter.h", _SHIM], ["-Wno-unknown-pragmas"]),
     "colour": ([_C + "k_colour.h", "include/svslam.h", _SHIM], ["-Wno-unknown-pragmas"]),
     "orb": ([_C + "k_orb.h"], ["-Wno-unknown-pragmas"]),
+    "orb_desc": ([_C + "k_orb_desc.h", _C + "k_orb.h", _C + "k_brief.h"], ["-Wno-unknown-pragmas"]),
 }
 
 

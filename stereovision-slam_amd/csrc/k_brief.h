@@ -234,53 +234,72 @@ BR_DEV bool br_row(const BrBuf &B, int total_pts, int wg, int tid, int *g, BrCtr
     return c->cx >= 0;
 }
 
+// the phases of one wave on its LDS block (shared with k_orb_desc.h): the patch whose first pixel is src, rows `pitch` apart
+BR_DEV void br_patch_load(uint8_t *patch, const uint8_t *src, size_t pitch, int P, int lane)
+{
+    const int sr = BR_WAVE / P, sx = BR_WAVE % P;
+    int r = lane / P, x = lane % P;
+    for (int i = lane; i < P * P; i += BR_WAVE) {
+        patch[i] = src[(size_t)r * pitch + x];
+        r += sr; x += sx;
+        if (x >= P) { x -= P; ++r; }
+    }
+}
+
+// horizontal: P rows of Bw sums
+BR_DEV void br_blur_h(const uint8_t *patch, uint16_t *hs, int P, int Bw, int lane)
+{
+    const int sr = BR_WAVE / Bw, sx = BR_WAVE % Bw;
+    int r = lane / Bw, x = lane % Bw;
+    for (int i = lane; i < P * Bw; i += BR_WAVE) {
+        const uint8_t *p = patch + r * P + x;
+        const int v = 18 * (p[0] + p[6]) + 34 * (p[1] + p[5]) + 49 * (p[2] + p[4]) + 54 * p[3];
+        hs[i] = (uint16_t)v;
+        r += sr; x += sx;
+        if (x >= Bw) { x -= Bw; ++r; }
+    }
+}
+
+// vertical: Bw rows of Bw blurred pixels
+BR_DEV void br_blur_v(const uint16_t *hs, uint8_t *bl, int Bw, int lane)
+{
+    for (int i = lane; i < Bw * Bw; i += BR_WAVE) {
+        const uint16_t *p = hs + i;            // (r, x) -> rows r .. r + 6 of the sums, same column
+        const int v = 18 * ((int)p[0] + (int)p[6 * Bw]) + 34 * ((int)p[Bw] + (int)p[5 * Bw]) + 49 * ((int)p[2 * Bw] + (int)p[4 * Bw])
+                      + 54 * (int)p[3 * Bw];
+        bl[i] = (uint8_t)((v + 32768) >> 16);
+    }
+}
+
+// lane < 8: dword `lane` of the descriptor from the 256 flags
+BR_DEV uint32_t br_pack(const uint8_t *bits, int lane)
+{
+    uint32_t v = 0;
+    for (int k = 0; k < 32; ++k) v |= (uint32_t)bits[32 * lane + k] << k;
+    return v;
+}
+
 BR_DEV void br_describe_run(const BrBuf &B, const BrImg &I, const BrPlan &L, int total_pts, int wg, unsigned char *smem)
 {
-    const int P = L.P, Bw = L.Bw;
     BR_PAR {                                           // the patch
         int g; BrCtr c;
-        if (br_row(B, total_pts, wg, tid, &g, &c)) {
-            const int lane = tid % BR_WAVE;
-            uint8_t *patch = smem + (size_t)(tid / BR_WAVE) * L.wave_bytes;
-            const uint8_t *src = I.base + (size_t)c.slot * I.slot_bytes + I.origin + (size_t)(c.cy - L.R) * I.pitch + (size_t)(c.cx - L.R);
-            const int sr = BR_WAVE / P, sx = BR_WAVE % P;
-            int r = lane / P, x = lane % P;
-            for (int i = lane; i < P * P; i += BR_WAVE) {
-                patch[i] = src[(size_t)r * I.pitch + x];
-                r += sr; x += sx;
-                if (x >= P) { x -= P; ++r; }
-            }
-        }
+        if (br_row(B, total_pts, wg, tid, &g, &c))
+            br_patch_load(smem + (size_t)(tid / BR_WAVE) * L.wave_bytes,
+                          I.base + (size_t)c.slot * I.slot_bytes + I.origin + (size_t)(c.cy - L.R) * I.pitch + (size_t)(c.cx - L.R),
+                          (size_t)I.pitch, L.P, tid % BR_WAVE);
     } BR_SYNC
-    BR_PAR {                                           // horizontal: P rows of Bw sums
+    BR_PAR {
         int g; BrCtr c;
         if (br_row(B, total_pts, wg, tid, &g, &c)) {
-            const int lane = tid % BR_WAVE;
-            const uint8_t *patch = smem + (size_t)(tid / BR_WAVE) * L.wave_bytes;
-            uint16_t *hs = (uint16_t *)(smem + (size_t)(tid / BR_WAVE) * L.wave_bytes + L.o_h);
-            const int sr = BR_WAVE / Bw, sx = BR_WAVE % Bw;
-            int r = lane / Bw, x = lane % Bw;
-            for (int i = lane; i < P * Bw; i += BR_WAVE) {
-                const uint8_t *p = patch + r * P + x;
-                const int v = 18 * (p[0] + p[6]) + 34 * (p[1] + p[5]) + 49 * (p[2] + p[4]) + 54 * p[3];
-                hs[i] = (uint16_t)v;
-                r += sr; x += sx;
-                if (x >= Bw) { x -= Bw; ++r; }
-            }
+            unsigned char *wv = smem + (size_t)(tid / BR_WAVE) * L.wave_bytes;
+            br_blur_h(wv, (uint16_t *)(wv + L.o_h), L.P, L.Bw, tid % BR_WAVE);
         }
     } BR_SYNC
-    BR_PAR {                                           // vertical: Bw rows of Bw blurred pixels
+    BR_PAR {
         int g; BrCtr c;
         if (br_row(B, total_pts, wg, tid, &g, &c)) {
-            const int lane = tid % BR_WAVE;
-            const uint16_t *hs = (const uint16_t *)(smem + (size_t)(tid / BR_WAVE) * L.wave_bytes + L.o_h);
-            uint8_t *bl = smem + (size_t)(tid / BR_WAVE) * L.wave_bytes + L.o_b;
-            for (int i = lane; i < Bw * Bw; i += BR_WAVE) {
-                const uint16_t *p = hs + i;            // (r, x) -> rows r .. r + 6 of the sums, same column
-                const int v = 18 * ((int)p[0] + (int)p[6 * Bw]) + 34 * ((int)p[Bw] + (int)p[5 * Bw]) + 49 * ((int)p[2 * Bw] + (int)p[4 * Bw])
-                              + 54 * (int)p[3 * Bw];
-                bl[i] = (uint8_t)((v + 32768) >> 16);
-            }
+            unsigned char *wv = smem + (size_t)(tid / BR_WAVE) * L.wave_bytes;
+            br_blur_v((const uint16_t *)(wv + L.o_h), wv + L.o_b, L.Bw, tid % BR_WAVE);
         }
     } BR_SYNC
     BR_PAR {                                           // the tests
@@ -296,12 +315,7 @@ BR_DEV void br_describe_run(const BrBuf &B, const BrImg &I, const BrPlan &L, int
         int g; BrCtr c;
         if (br_row(B, total_pts, wg, tid, &g, &c)) {
             const int lane = tid % BR_WAVE;
-            if (lane < 8) {
-                const uint8_t *bits = smem + (size_t)(tid / BR_WAVE) * L.wave_bytes + L.o_bits + 32 * lane;
-                uint32_t v = 0;
-                for (int k = 0; k < 32; ++k) v |= (uint32_t)bits[k] << k;
-                B.desc[8 * (size_t)g + lane] = v;
-            }
+            if (lane < 8) B.desc[8 * (size_t)g + lane] = br_pack(smem + (size_t)(tid / BR_WAVE) * L.wave_bytes + L.o_bits, lane);
         }
     } BR_SYNC
 }

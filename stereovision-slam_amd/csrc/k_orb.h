@@ -171,6 +171,18 @@ static inline void orb_axis_taps(int src, int dst, OrbTap *t)
     }
 }
 
+// scale and size of level l of a w x h image (svslam_orb_describe_batch builds its levels from the same rule)
+static inline void orb_level_size(int w, int h, int l, float *scale, int *lw, int *lh)
+{
+    *scale = (float)pow((double)1.2f, (double)l);
+    if (l == 0) { *lw = w; *lh = h; return; }
+    const float inv = 1.0f / *scale;
+    *lw = orb_round_even((float)w * inv);
+    *lh = orb_round_even((float)h * inv);
+    if (*lw < 1) *lw = 1;
+    if (*lh < 1) *lh = 1;
+}
+
 static inline size_t orb_up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // Every host rule of a call: the parameters' defaults and refusals, level sizes, quotas, resize tables, a job's block, the chunks.
@@ -219,14 +231,8 @@ static inline const char *orb_plan(OrbPlan &P, int w, int h, int nslots, int njo
     size_t o = 0;
     for (int l = 0; l < nl; ++l) {
         OrbLevel &L = G.L[l];
-        L.scale = (float)pow((double)1.2f, (double)l);
-        if (l == 0) { L.w = w; L.h = h; }
-        else {
-            const float inv = 1.0f / L.scale;
-            L.w = orb_round_even((float)w * inv);
-            L.h = orb_round_even((float)h * inv);
-            if (L.w < 1) L.w = 1;
-            if (L.h < 1) L.h = 1;
+        orb_level_size(w, h, l, &L.scale, &L.w, &L.h);
+        if (l > 0) {
             L.xtap = (int)P.taps.size();
             P.taps.resize(P.taps.size() + (size_t)L.w);
             orb_axis_taps(G.L[l - 1].w, L.w, P.taps.data() + L.xtap);
@@ -376,32 +382,37 @@ ORB_DEV void orb_rect_run(const OrbGeom &G, const OrbBuf &B, int r)
     }
 }
 
-// ---- resize: flat pixels [4 t, 4 t + 4) of level l, image (which == 0) or mask -------------------------------------------------------
-ORB_DEV void orb_resize_task(const OrbGeom &G, const OrbImg &I, const OrbBuf &B, int l, int j, int which, int t)
+// ---- resize: flat pixels [4 t, 4 t + 4) of a w-wide level of n pixels from src by the axes' taps; which == 1: a mask -------------------------
+ORB_DEV void orb_resize_px4(const uint8_t *src, int pitch, uint8_t *dst, const OrbTap *xt, const OrbTap *yt, int w, int n, int which, int t)
 {
-    const OrbLevel &L = G.L[l];
-    const int n = L.w * L.h;
     if (4 * t >= n) return;
-    OrbView S;
-    uint8_t *dst;
-    if (which == 0) { S = orb_image(G, I, B, j, l - 1); dst = B.blocks + (size_t)j * G.job_bytes + L.img; }
-    else { S.p = B.blocks + (size_t)j * G.job_bytes + G.L[l - 1].mask; S.pitch = G.L[l - 1].w; dst = B.blocks + (size_t)j * G.job_bytes + L.mask; }
-    const OrbTap *xt = B.taps + L.xtap, *yt = B.taps + L.ytap;
     uint32_t word = 0;
-    int y = (4 * t) / L.w, x = 4 * t - y * L.w;
+    int y = (4 * t) / w, x = 4 * t - y * w;
     for (int k = 0; k < 4; ++k) {
         if (4 * t + k < n) {
             const OrbTap tx = xt[x], ty = yt[y];
-            const uint8_t *r0 = S.p + (size_t)ty.i0 * S.pitch, *r1 = S.p + (size_t)ty.i1 * S.pitch;
+            const uint8_t *r0 = src + (size_t)ty.i0 * pitch, *r1 = src + (size_t)ty.i1 * pitch;
             const int t0 = (int)r0[tx.i0] * tx.c0 + (int)r0[tx.i1] * tx.c1;
             const int t1 = (int)r1[tx.i0] * tx.c0 + (int)r1[tx.i1] * tx.c1;
             uint32_t v = (uint32_t)(t0 * (int)ty.c0 + t1 * (int)ty.c1 + 32768) >> 16;
             if (which == 1 && v <= 254u) v = 0;
             word |= v << (8 * k);
         }
-        if (++x == L.w) { x = 0; ++y; }
+        if (++x == w) { x = 0; ++y; }
     }
     ((uint32_t *)dst)[t] = word;
+}
+
+// level l of job j, image (which == 0) or mask
+ORB_DEV void orb_resize_task(const OrbGeom &G, const OrbImg &I, const OrbBuf &B, int l, int j, int which, int t)
+{
+    const OrbLevel &L = G.L[l];
+    if (4 * t >= L.w * L.h) return;
+    OrbView S;
+    uint8_t *dst;
+    if (which == 0) { S = orb_image(G, I, B, j, l - 1); dst = B.blocks + (size_t)j * G.job_bytes + L.img; }
+    else { S.p = B.blocks + (size_t)j * G.job_bytes + G.L[l - 1].mask; S.pitch = G.L[l - 1].w; dst = B.blocks + (size_t)j * G.job_bytes + L.mask; }
+    orb_resize_px4(S.p, S.pitch, dst, B.taps + L.xtap, B.taps + L.ytap, L.w, L.w * L.h, which, t);
 }
 
 // ---- FAST --------------------------------------------------------------------------------------------------------------------------

@@ -56,6 +56,7 @@ typedef enum { ncclDouble = 8 } ncclDataType_t;
 #include "k_global_desc.h"
 #include "k_colour.h"
 #include "k_orb.h"
+#include "k_orb_desc.h"
 
 #define SVSLAM_DMAP_CHUNK 512     /* keyframe jobs per svslam_dmap_keyframe_batch call the staging arena is sized for */
 #define SVSLAM_DMAP_EVICT_PER_JOB 512   /* evicted-landmark records per job of a call (shared by the call's jobs; the surplus waits) */
@@ -76,6 +77,7 @@ enum { FAM_PYR = 0, FAM_LK, FAM_GFTT, FAM_TRI, FAM_POSE, FAM_BA,
        FAM_COL,        // 18: "colour", k_bgr_prepare of svslam_pyramid_bgr_batch (units = images); appended, nothing moved
        FAM_LF,         // 19: "local_fusion", svslam_local_fusion_batch (units = jobs); appended, nothing moved
        FAM_ORB,        // 20: "orb", svslam_orb_detect_batch (units = jobs); appended, nothing moved
+       FAM_ORBD,       // 21: "orb_desc", svslam_orb_describe_batch (units = points); appended, nothing moved
        FAM_COUNT };
 
 struct Timing {
@@ -148,6 +150,9 @@ struct svslam_ctx {
     // ORB detector (svslam_orb_detect_batch): one device buffer (tables, jobs, rects, results, the jobs' levels, maps and lists of a
     // chunk) and its pageable host mirror of the uploaded part and the results; the last call's plan stays for svslam_orb_read_level
     struct : DevBuf { OrbPlan plan; bool have = false; } orb;
+    // ORB descriptors (svslam_orb_describe_batch): one device buffer (geometry, tables, points, rows, results, the jobs' levels of a
+    // chunk) and its host mirror of the uploaded part and the results
+    struct : DevBuf { OdPlan plan; } orbd;
     // loop candidates: the resident store of normalised global descriptors (S on the device, H its bookkeeping) and a call's staging
     struct : DevBuf { LcStore S = {}; LcHost H; } lc;
     // global descriptor (svslam_gdesc_*): the configured network, its parameters and resize tables on the device, the workspace of a
@@ -859,4 +864,5 @@ int svslam_timing_get(svslam_ctx *c, int family, double *total_ms, long long *la
 #include "api_dmap.h"
 #include "api_loop.h"
 #include "api_orb.h"
+#include "api_orb_desc.h"
 #include "api_debug.h"

@@ -133,6 +133,8 @@ public:
                     const uint8_t *has_xyz, int total_q, const uint8_t *desc_q, const float *uv_q, int *mc, int *mq, int *md, uint8_t *mi)
     { return svslam_loop_verify_batch(ctx_, n, jobs, prm, total_c, desc_c, xyz_c, has_xyz, total_q, desc_q, uv_q, mc, mq, md, mi); }
 
+    int orb_describe(int n, svslam_orb_desc_job *jobs, const svslam_orb_desc_params *prm, int total_pts, const svslam_orb_kp *kps, uint8_t *desc, int *desc_pt)
+    { return svslam_orb_describe_batch(ctx_, n, jobs, prm, total_pts, kps, desc, desc_pt); }
     int brief_describe(int n, svslam_brief_job *jobs, const svslam_brief_params *prm, int total_pts, const float *xy, uint8_t *desc, int *desc_pt)
     { return svslam_brief_describe_batch(ctx_, n, jobs, prm, total_pts, xy, desc, desc_pt); }
 

@@ -106,6 +106,30 @@ extern "C" int svs_pipe_describe_new_keyframes(void *p, const void *brief_params
         return -1;
     }
 }
+extern "C" int svs_pipe_describe_new_keyframes_oriented(void *p, const void *orb_desc_params_or_null)
+{
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    try {
+        int n = 0;
+        if (!h->pipe->DescribeNewKeyframesOriented(static_cast<const svslam_orb_desc_params *>(orb_desc_params_or_null), &n)) { g_err = h->pipe->last_error(); return -1; }
+        return n;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+extern "C" long long svs_pipe_keyframe_keypoints(void *p, int stream, long long kf_id, float *rows4, long long cap)
+{
+    PipeHandle *h = static_cast<PipeHandle *>(p);
+    try {
+        const long n = h->pipe->KeyframeKeypoints(stream, (long)kf_id, rows4, (long)cap);
+        if (n < 0) g_err = h->pipe->last_error();
+        return n;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
 extern "C" long long svs_pipe_keyframe_descriptors(void *p, int stream, long long kf_id, uint8_t *desc32, int *feat, long long cap)
 {
     PipeHandle *h = static_cast<PipeHandle *>(p);

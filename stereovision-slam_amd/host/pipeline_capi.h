@@ -109,6 +109,14 @@ int svs_pipe_verify_loops(void *p, int nqueries, const svs_loop_query *queries, 
  * degree, edge 31.  Returns the number of keyframes described, -1 (svs_pipe_last_error, nothing stored): the map lives on the device
  * (device_map = 1), the kernel's refusal.  Product library only. */
 int svs_pipe_describe_new_keyframes(void *p, const void *brief_params_or_null);
+/* svs_pipe_describe_new_keyframes with every feature described at its own angle and octave (svslam_orb_describe_batch): what
+ * cv::ORB::compute gives the reference when keypoint_feature_detector is ORB.  A tracked feature and a GFTT corner carry -1 degree and
+ * octave 0, so with GFTT the stored rows are svs_pipe_describe_new_keyframes' rows.  orb_desc_params_or_null: svslam_orb_desc_params or
+ * NULL for the default table, edge 31, 8 levels.  Returns and refusals as svs_pipe_describe_new_keyframes.  Product library only. */
+int svs_pipe_describe_new_keyframes_oriented(void *p, const void *orb_desc_params_or_null);
+/* x, y, angle, octave of every left feature of keyframe kf_id, rows4 [n][4] floats in the order of svs_pipe_keyframe_features: what
+ * the oriented descriptors were computed at.  Returns n (nothing is written when cap < n or rows4 is NULL), -1 for a bad stream / id. */
+long long svs_pipe_keyframe_keypoints(void *p, int stream, long long kf_id, float *rows4, long long cap);
 /* the stored descriptors of keyframe kf_id: desc32 [n][32] and feat [n] = index of each row's feature in the keyframe's left list.
  * Returns n (nothing is written when cap < n or an array is NULL: call again), -1 for a bad stream / id or a keyframe that was never
  * described (a keyframe described with zero rows returns 0). */

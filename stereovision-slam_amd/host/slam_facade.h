@@ -288,6 +288,8 @@ struct FrontendOptions {            // the hyper-parameters Frontend::Frontend()
     // features, LoopClosure::ExtractKeypointsDescriptor) and keyframes keep their feature lists when they leave the window, so
     // that VerifyLoop(kf, cand, out) needs no descriptors from the caller.  `loop_descriptors: 1` in the YAML (or this field);
     // 0 (default): nothing is described, behaviour and memory as without the key.  Needs the host map (device_map: 0).
+    // 2: the same with every feature described at its own angle and octave (Pipeline::DescribeNewKeyframesOriented,
+    // svslam_orb_describe_batch): what the reference gets with the ORB detector.  With GFTT, 2 gives the bits of 1.
     int loop_descriptors = 0;
     // Frontend::DetectLoop's store of global descriptors: `loop_store_capacity` keyframes of `loop_descriptor_dim` floats (the
     // reference's vector has 1280); allocated at the first DetectLoop, never without it
@@ -298,7 +300,7 @@ struct FrontendOptions {            // the hyper-parameters Frontend::Frontend()
     std::string loop_global_descriptor;
     // `keypoint_feature_detector: ORB` of the reference's configuration (src/frontend.cpp:20-33): 1 = the ORB detector
     // (Pipeline::SetDetector, svslam_orb_detect_batch), which selects the host map; 0 (default, `GFTT`): goodFeaturesToTrack.
-    // Any other value of the key throws.  ORB with loop_descriptors = 1 throws: the descriptors are not steered per keypoint yet.
+    // Any other value of the key throws.  ORB with loop_descriptors = 1 throws (one angle, level 0: wrong for ORB keypoints); 2 is its value.
     int detector = 0;
     static FrontendOptions FromConfig(const ConfigFile &c)
     {
@@ -321,8 +323,9 @@ struct FrontendOptions {            // the hyper-parameters Frontend::Frontend()
         const std::string det = c.Str("keypoint_feature_detector", "GFTT");
         if (det == "ORB") o.detector = 1;
         else if (det != "GFTT") throw SLAMException("Only the GFTT and ORB keypoint detectors are on the GPU path");
-        if (o.detector == 1 && o.loop_descriptors)
-            throw SLAMException("keypoint_feature_detector: ORB with loop_descriptors: 1 is not supported yet: the descriptors would ignore the keypoints' angle and octave");
+        if (o.loop_descriptors < 0 || o.loop_descriptors > 2) throw SLAMException("loop_descriptors: the values are 0 (none), 1 (one angle, level 0) and 2 (each keypoint's angle and octave)");
+        if (o.detector == 1 && o.loop_descriptors == 1)
+            throw SLAMException("keypoint_feature_detector: ORB with loop_descriptors: 1 is not supported: 1 describes every feature at one angle on level 0; use loop_descriptors: 2, which describes each at its keypoint's angle and octave");
         return o;
     }
 };
@@ -479,7 +482,13 @@ private:
     // (a function of its own so that a provider without the kernel never instantiates Pipeline::DescribeNewKeyframes)
     void describe_new_keyframe()
     {
-        if constexpr (provider_has_brief<K>(0)) {
+        if (opt_.loop_descriptors == 2) {
+            if constexpr (provider_has_orb_describe<K>(0)) {
+                if (!pipe_->DescribeNewKeyframesOriented()) throw SLAMException(pipe_->last_error());
+            } else {
+                throw SLAMException("loop_descriptors: 2: this kernel provider has no oriented descriptors");
+            }
+        } else if constexpr (provider_has_brief<K>(0)) {
             if (!pipe_->DescribeNewKeyframes()) throw SLAMException(pipe_->last_error());
         } else {
             throw SLAMException("loop_descriptors: this kernel provider has no descriptor kernel");
@@ -511,8 +520,9 @@ private:
         cfg.num_active_keyframes = opt_.num_active_keyframes; cfg.chi2_th = opt_.chi2_th;
         cfg.backend_on = 1;                        // gated by SetBackendEnabled: see SetBackend
         cfg.width = dw; cfg.height = dh; cfg.src_width = w; cfg.src_height = h;
-        if (opt_.detector == 1 && opt_.loop_descriptors)
-            throw SLAMException("keypoint_feature_detector: ORB with loop_descriptors: 1 is not supported yet: the descriptors would ignore the keypoints' angle and octave");
+        if (opt_.loop_descriptors < 0 || opt_.loop_descriptors > 2) throw SLAMException("loop_descriptors: the values are 0 (none), 1 (one angle, level 0) and 2 (each keypoint's angle and octave)");
+        if (opt_.detector == 1 && opt_.loop_descriptors == 1)
+            throw SLAMException("keypoint_feature_detector: ORB with loop_descriptors: 1 is not supported: 1 describes every feature at one angle on level 0; use loop_descriptors: 2, which describes each at its keypoint's angle and octave");
         const bool dmap = opt_.device_map != 0 && provider_has_device_map<K>(0) && cfg.num_active_keyframes + 1 <= 12 && opt_.detector == 0;
         cfg.resident_track = dmap ? 1 : 0;         // host map: the host keeps the feature lists; device map: nothing per feature on the host
         cfg.device_map = dmap ? 1 : 0;

@@ -80,7 +80,12 @@ struct Feature {
     float x = 0, y = 0;
     long mp = -1;        // map point id, -1 == expired weak_ptr
     bool outlier = false;
+    // cv::KeyPoint's octave and angle of position_ (src/frontend.cpp:51-58): what ORB::detect gave a freshly detected feature; a tracked
+    // one is cv::KeyPoint(pt, 7) (:374), angle -1 and octave 0, and so is a GFTT corner.  Both live in what was the struct's padding
+    int8_t octave = 0;
+    float angle = -1.f;
 };
+static_assert(sizeof(Feature) == 24, "angle and octave live in Feature's padding: the host map pays nothing for them");
 
 struct Frame {
     long id = 0;
@@ -510,6 +515,9 @@ struct Stream {
 // does the kernel provider offer the ORB detector (HipKernels::orb_detect)?  The providers of the CPU twins do not.
 template <class K> constexpr auto provider_has_orb(int) -> decltype(&K::orb_detect, true) { return true; }
 template <class K> constexpr bool provider_has_orb(long) { return false; }
+// and the oriented descriptors (HipKernels::orb_describe)?
+template <class K> constexpr auto provider_has_orb_describe(int) -> decltype(&K::orb_describe, true) { return true; }
+template <class K> constexpr bool provider_has_orb_describe(long) { return false; }
 
 template <class K>
 class Pipeline {
@@ -914,40 +922,95 @@ public:
         if (n_described) *n_described = 0;
         if (device_map()) return refuse("DescribeNewKeyframes: with device_map = 1 the keyframes' features live on the device; not supported yet");
         Flush();
-        std::vector<Frame *> kfs;
-        std::vector<svslam_brief_job> jobs;
-        std::vector<std::vector<int>> sel;
-        std::vector<float> xy;
-        for (auto &stp : streams_) {
-            Frame *f = stp->last;
-            if (!f || !f->is_keyframe || f->described) continue;
-            svslam_brief_job J;
-            std::memset(&J, 0, sizeof(J));
-            J.slot = stp->slot_cur; J.pt_ofs = (int)(xy.size() / 2);
-            sel.emplace_back();
-            for (size_t i = 0; i < f->left.size(); ++i)
-                if (!f->left[i].outlier) { sel.back().push_back((int)i); xy.push_back(f->left[i].x); xy.push_back(f->left[i].y); }
-            J.npts = (int)sel.back().size();
-            jobs.push_back(J); kfs.push_back(f);
-        }
-        if (kfs.empty()) return true;
+        DescribeSet D;
+        CollectUndescribed(D);
+        if (D.kfs.empty()) return true;
+        const int total = (int)D.feats.size();
+        std::vector<svslam_brief_job> jobs(D.kfs.size());
+        for (size_t j = 0; j < jobs.size(); ++j) { std::memset(&jobs[j], 0, sizeof(jobs[j])); jobs[j].slot = D.slot[j]; jobs[j].pt_ofs = D.ofs[j]; jobs[j].npts = (int)D.sel[j].size(); }
+        std::vector<float> xy(2 * (size_t)total + 2);
+        for (int i = 0; i < total; ++i) { xy[2 * (size_t)i] = D.feats[(size_t)i]->x; xy[2 * (size_t)i + 1] = D.feats[(size_t)i]->y; }
         svslam_brief_params P;
         if (params) P = *params; else { P.pattern = nullptr; P.angle_deg = -1.0f; P.edge = 31; }
-        const int total = (int)(xy.size() / 2);
         std::vector<uint8_t> desc(32 * (size_t)total + 1);
         std::vector<int> dpt((size_t)total + 1);
         if (k_.brief_describe((int)jobs.size(), jobs.data(), &P, total, xy.data(), desc.data(), dpt.data()) != 0)
             return refuse(std::string("DescribeNewKeyframes: ") + k_.last_error());
-        for (size_t j = 0; j < kfs.size(); ++j) {
-            Frame *f = kfs[j];
-            const svslam_brief_job &J = jobs[j];
-            f->desc.assign(desc.begin() + 32 * (size_t)J.pt_ofs, desc.begin() + 32 * ((size_t)J.pt_ofs + (size_t)J.n_desc));
-            f->desc_feat_indx.resize((size_t)J.n_desc);
-            for (int r = 0; r < J.n_desc; ++r) f->desc_feat_indx[(size_t)r] = sel[j][(size_t)dpt[(size_t)J.pt_ofs + (size_t)r]];
-            f->described = true;
-        }
-        if (n_described) *n_described = (int)kfs.size();
+        for (size_t j = 0; j < jobs.size(); ++j) StoreDescriptors(D, j, jobs[j].n_desc, desc, dpt);
+        if (n_described) *n_described = (int)D.kfs.size();
         return true;
+    }
+    // DescribeNewKeyframes with every feature described at its own angle and octave (svslam_orb_describe_batch): what
+    // cv::ORB::compute does with Feature::position_ when the detector is ORB.  The same selection rule, storage and refusals; a
+    // tracked feature and a GFTT corner carry -1 degree and octave 0, so with GFTT the rows are DescribeNewKeyframes' rows.
+    // params: nullptr for the default table, edge 31, 8 levels.  Instantiated only where it is called: the provider needs orb_describe.
+    bool DescribeNewKeyframesOriented(const svslam_orb_desc_params *params = nullptr, int *n_described = nullptr)
+    {
+        if (n_described) *n_described = 0;
+        if (device_map()) return refuse("DescribeNewKeyframesOriented: with device_map = 1 the keyframes' features live on the device; not supported yet");
+        Flush();
+        DescribeSet D;
+        CollectUndescribed(D);
+        if (D.kfs.empty()) return true;
+        const int total = (int)D.feats.size();
+        std::vector<svslam_orb_desc_job> jobs(D.kfs.size());
+        for (size_t j = 0; j < jobs.size(); ++j) { std::memset(&jobs[j], 0, sizeof(jobs[j])); jobs[j].slot = D.slot[j]; jobs[j].pt_ofs = D.ofs[j]; jobs[j].npts = (int)D.sel[j].size(); }
+        std::vector<svslam_orb_kp> kps((size_t)total + 1);
+        for (int i = 0; i < total; ++i) { const Feature &F = *D.feats[(size_t)i]; kps[(size_t)i] = svslam_orb_kp{ F.x, F.y, 0.f, F.angle, 0.f, (int)F.octave }; }
+        svslam_orb_desc_params P;
+        if (params) P = *params; else std::memset(&P, 0, sizeof(P));
+        std::vector<uint8_t> desc(32 * (size_t)total + 1);
+        std::vector<int> dpt((size_t)total + 1);
+        if (k_.orb_describe((int)jobs.size(), jobs.data(), &P, total, kps.data(), desc.data(), dpt.data()) != 0)
+            return refuse(std::string("DescribeNewKeyframesOriented: ") + k_.last_error());
+        for (size_t j = 0; j < jobs.size(); ++j) StoreDescriptors(D, j, jobs[j].n_desc, desc, dpt);
+        if (n_described) *n_described = (int)D.kfs.size();
+        return true;
+    }
+    // what both describe calls share.  CollectUndescribed: every stream whose last step made a keyframe that has no descriptors yet,
+    // its slot, the indices of its non-outlier left features (sel) and those features in one list, job j's from ofs[j] on.
+    // StoreDescriptors: the first n_desc rows of job j become the keyframe's; desc_feat_indx[row] = the feature's own index.
+    struct DescribeSet {
+        std::vector<Frame *> kfs;
+        std::vector<int> slot, ofs;
+        std::vector<std::vector<int>> sel;
+        std::vector<const Feature *> feats;
+    };
+    void CollectUndescribed(DescribeSet &D)
+    {
+        for (auto &stp : streams_) {
+            Frame *f = stp->last;
+            if (!f || !f->is_keyframe || f->described) continue;
+            D.kfs.push_back(f); D.slot.push_back(stp->slot_cur); D.ofs.push_back((int)D.feats.size());
+            D.sel.emplace_back();
+            for (size_t i = 0; i < f->left.size(); ++i)
+                if (!f->left[i].outlier) { D.sel.back().push_back((int)i); D.feats.push_back(&f->left[i]); }
+        }
+    }
+    static void StoreDescriptors(const DescribeSet &D, size_t j, int n_desc, const std::vector<uint8_t> &desc, const std::vector<int> &dpt)
+    {
+        Frame *f = D.kfs[j];
+        const size_t o = (size_t)D.ofs[j];
+        f->desc.assign(desc.begin() + 32 * o, desc.begin() + 32 * (o + (size_t)n_desc));
+        f->desc_feat_indx.resize((size_t)n_desc);
+        for (int r = 0; r < n_desc; ++r) f->desc_feat_indx[(size_t)r] = D.sel[j][(size_t)dpt[o + (size_t)r]];
+        f->described = true;
+    }
+    // x, y, angle, octave of every left feature of a keyframe, in the order of keyframe_features: what a test compares the stored rows
+    // with.  rows: [n][4] floats or nullptr; returns n, or -1 for a bad stream / id
+    long KeyframeKeypoints(int s, long kf_id, float *rows, long cap)
+    {
+        if (s < 0 || s >= nstreams()) { refuse("KeyframeKeypoints: no such stream"); return -1; }
+        const std::vector<Frame *> &kfs = streams_[s]->map.keyframes_;
+        if (kf_id < 0 || kf_id >= (long)kfs.size()) { refuse("KeyframeKeypoints: not a keyframe id of this stream"); return -1; }
+        const Frame *f = kfs[(size_t)kf_id];
+        const long n = (long)f->left.size();
+        if (rows && cap >= n)
+            for (long i = 0; i < n; ++i) {
+                const Feature &F = f->left[(size_t)i];
+                rows[4 * i] = F.x; rows[4 * i + 1] = F.y; rows[4 * i + 2] = F.angle; rows[4 * i + 3] = (float)F.octave;
+            }
+        return n;
     }
     // the stored descriptors of a keyframe, read-only: rows of 32 bytes and desc_feat_indx.  False: a bad stream / id, or a keyframe
     // that was never described (which is not a keyframe described with zero rows)
@@ -1683,7 +1746,7 @@ private:
 
     // keypoint_feature_detector: ORB (src/frontend.cpp:20-33, :51): cv::ORB::create(num_features)->detect(img, kps, mask) through the
     // provider's orb_detect with the rects DetectFeatures has filled; (x, y) of the keypoints are appended under the same max_pts /
-    // c_dropped rule as the corners.  Feature keeps x and y only for now: angle, octave, size and response are not stored.
+    // c_dropped rule as the corners, with their angle and octave (DescribeNewKeyframesOriented reads them); size and response are not stored.
     // Keypoints the rules give beyond the call's 2 num_features rows (score and response ties) count as dropped.
     void DetectOrb(const std::vector<int> &DS, int n, int ofs)
     {
@@ -1711,6 +1774,8 @@ private:
                     Feature f;
                     f.x = kps_orb_[(size_t)i * max_out + c].x;
                     f.y = kps_orb_[(size_t)i * max_out + c].y;
+                    f.angle = kps_orb_[(size_t)i * max_out + c].angle;
+                    f.octave = (int8_t)kps_orb_[(size_t)i * max_out + c].octave;
                     st.current->left.push_back(f);
                 }
                 st.c_corners += take;

@@ -155,6 +155,10 @@ def _bind(L):
         L.svs_pipe_keyframe_descriptors.restype = C.c_longlong
         L.svs_pipe_keyframe_descriptors.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong]
         L.svs_pipe_verify_loops_stored.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
+    if hasattr(L, "svs_pipe_describe_new_keyframes_oriented"):
+        L.svs_pipe_describe_new_keyframes_oriented.argtypes = [C.c_void_p, C.c_void_p]
+        L.svs_pipe_keyframe_keypoints.restype = C.c_longlong
+        L.svs_pipe_keyframe_keypoints.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_longlong]
     if hasattr(L, "svs_pipe_detect_loops"):
         L.svs_pipe_loopdb_configure.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.svs_pipe_detect_loops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -347,20 +351,41 @@ class Pipeline:
             row += len(keep[i][2])
         return out
 
-    def describe_new_keyframes(self, pattern=None, angle_deg=-1.0, edge=31):
+    def describe_new_keyframes(self, pattern=None, angle_deg=-1.0, edge=31, oriented=False, nlevels=0):
         """LoopClosure::ExtractKeypointsDescriptor for every stream whose last step made a keyframe (svs_pipe_describe_new_keyframes):
         BRIEF-256 at the keyframe's non-outlier left features, stored with the keyframe.  Call it after step() and before the next
-        one.  pattern / angle_deg / edge: as Context.brief_describe.  Returns the number of keyframes described."""
+        one.  pattern / angle_deg / edge: as Context.brief_describe.  Returns the number of keyframes described.
+        oriented=True (svs_pipe_describe_new_keyframes_oriented): every feature at its own angle and octave, as Context.orb_describe
+        (angle_deg is not used; nlevels 0 is 8)."""
         import importlib
         _svs = importlib.import_module(__package__)
         pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
         if pat is not None and pat.size != 1024:
             raise ValueError("describe_new_keyframes: the table has %d entries, not 256 x 4" % pat.size)
+        if oriented:
+            if not hasattr(self.L, "svs_pipe_describe_new_keyframes_oriented"):
+                raise RuntimeError("describe_new_keyframes(oriented=True): this pipeline library has no oriented descriptors")
+            P = _svs.OrbDescParams(None if pat is None else pat.ctypes.data, int(edge), int(nlevels), 0)
+            n = self.L.svs_pipe_describe_new_keyframes_oriented(self.h, C.byref(P))
+            if n < 0:
+                raise RuntimeError("svs_pipe_describe_new_keyframes_oriented refused: " + self.L.svs_pipe_last_error().decode())
+            return n
         P = _svs.BriefParams(None if pat is None else pat.ctypes.data, float(angle_deg), int(edge))
         n = self.L.svs_pipe_describe_new_keyframes(self.h, C.byref(P))
         if n < 0:
             raise RuntimeError("svs_pipe_describe_new_keyframes refused: " + self.L.svs_pipe_last_error().decode())
         return n
+
+    def keyframe_keypoints(self, stream, kf_id):
+        """x, y, angle, octave of every left feature of a keyframe (svs_pipe_keyframe_keypoints), [n, 4] f32 in the order of
+        keyframe_features: what describe_new_keyframes(oriented=True) describes"""
+        n = self.L.svs_pipe_keyframe_keypoints(self.h, int(stream), C.c_longlong(kf_id), None, 0)
+        if n < 0:
+            raise RuntimeError("svs_pipe_keyframe_keypoints refused: " + self.L.svs_pipe_last_error().decode())
+        rows = np.zeros((n, 4), np.float32)
+        if n and self.L.svs_pipe_keyframe_keypoints(self.h, int(stream), C.c_longlong(kf_id), rows.ctypes.data_as(C.c_void_p), n) != n:
+            raise RuntimeError("svs_pipe_keyframe_keypoints changed size between two calls")
+        return rows
 
     def keyframe_descriptors(self, stream, kf_id):
         """the stored descriptors of a keyframe (svs_pipe_keyframe_descriptors): desc [n, 32] u8 and feat [n] int32, the index of each
